@@ -6,8 +6,8 @@ Metric (BASELINE.json): "device-resident packet-obfs GiB/s @ 1200B datagrams,
 datagram) over the whole synthetic batch, inputs already resident in HBM.
 
   * N = 1: BASELINE.json configs[1] -- 1,048,576 x 1200 B datagrams, one batch.
-    The line also carries a `bimodal` object: configs[2], 4M datagrams of the
-    40 % 64 B / 60 % 1350 B mix, packed output.
+    With --full the line also carries a `bimodal` object: configs[2], 4M
+    datagrams of the 40 % 64 B / 60 % 1350 B mix, packed output.
   * N > 1: BASELINE.json configs[3] -- 8,388,608 x 1200 B datagrams per GPU
     (64M over 8 GPUs), one process per GPU; rank r owns datagrams
     [r*P, (r+1)*P) of the global synthetic batch (weak scaling, no collective
@@ -28,9 +28,17 @@ Warm load: whatever runs in a cold GPU's first ~10 ms of sustained load slows by
 up to 12 % (a GPU power-state transient: per-call kernel traces with either
 direction first, profiles/r05_transient/).  Each workload therefore first runs a
 fixed warm load -- alternating obfuscate and deobfuscate steps for at least
-WARM_LOAD_MS of wall time -- and then times its deobfuscate pass and its obfuscate
-pass (the headline), each after the same W warm-up steps: both directions are
-measured at the rate a busy serving GPU sustains.
+WARM_LOAD_MS of wall time -- and then times its obfuscate pass (the headline) after
+W warm-up steps, at the rate a busy serving GPU sustains.
+
+A plain run does that and no more: set up, warm load, W + K obfuscate steps, the
+line (metric, value, ms_per_step, the event-timed roofline of those K steps).
+--full adds everything else, as the line carried it before the option existed: the
+timed deobfuscate pass (before the obfuscate pass, after the same W warm-up steps),
+the PMC traffic lookup, parity (round trip, configs[1] digest), the configs[2]
+`bimodal` object at N = 1 and cpu_baseline.  --no-parity, --no-bimodal,
+--no-cpu-baseline and --cpu-seconds trim a --full run.  --dump-outputs DIR writes
+what the last timed obfuscate step produced (dump_outputs below).
 """
 from __future__ import annotations
 
@@ -74,6 +82,11 @@ def parse():
     ap.add_argument("--no-bimodal", action="store_true", help="N=1: skip the configs[2] sub-object")
     ap.add_argument("--kernel", choices=["auto", "wave", "tile", "flat"], default="auto")
     ap.add_argument("--warm-load-ms", type=float, default=WARM_LOAD_MS)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the timed deobfuscate leg, PMC traffic, parity, the configs[2] "
+                         "sub-object (N = 1) and the CPU baseline (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed obfuscate step produced as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -248,7 +261,57 @@ def setup_bimodal(hy, obfs, dev, P, first):
                                out_off=out_off, out_len=out_len, workspace=ws, workspace_bytes=ws.numel())
     return dict(obf=step_obf, deobf=step_deobf, payload=total_in, obf_bytes=2 * total_in + 16 * P,
                 deobf_bytes=2 * total_in + 8 * P, inp=inp, wire=wire, back=back, n=P, len="bimodal",
-                kernel=kernel)
+                kernel=kernel, out_off=out_off, out_len=out_len)
+
+
+DUMP_SEED = 20240607        # --dump-outputs: which blocks / entries of a large output are kept
+DUMP_BLOCK = 4096           # bytes per sampled wire block
+DUMP_BLOCKS = 2048          # sampled wire blocks (32 MiB as float32)
+DUMP_SUM_BLOCKS = 1 << 20   # at most this many whole blocks in wire_block_sums
+DUMP_ENTRIES = 1 << 20      # sampled entries of a per-datagram output array
+
+
+def dump_outputs(w, outdir: str, suffix: str = "") -> None:
+    """--dump-outputs: what the obfuscate call of the last timed step returned, as .npy files
+    (well under 64 MB in all).  The wire (1.2 GB and more) is written as
+      wire_block_sums   float64, the byte sum of every block of the whole wire (blocks of
+                        4096 B, doubled until at most 2^20 of them; the last one may be short),
+      wire_sample       float32 [DUMP_BLOCKS + 1, 4096]: the bytes of DUMP_BLOCKS 4096-byte
+                        blocks drawn with a fixed seed, in ascending order, and of the wire's
+                        last 4096 bytes;
+    the ragged workload adds out_off_sample (float64) and out_len_sample (float32), the same
+    seeded DUMP_ENTRIES entries of both arrays.  Inputs, salts and the draws are seeded, so
+    two builds write comparable files."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    wire = w["wire"]
+    dev, total = wire.device, wire.numel()
+
+    def save(name, t):
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), t.cpu().numpy())
+
+    sb = min(DUMP_BLOCK, total)
+    while total // sb > DUMP_SUM_BLOCKS:
+        sb *= 2
+    whole = total // sb * sb
+    sums = [wire[:whole].view(-1, sb).sum(dim=1, dtype=torch.int64)]
+    if whole < total:
+        sums.append(wire[whole:].sum(dtype=torch.int64).reshape(1))
+    save("wire_block_sums", torch.cat(sums).to(torch.float64))
+
+    b = min(DUMP_BLOCK, total)
+    nb = total // b
+    pick = np.sort(rng.choice(nb, size=min(nb, DUMP_BLOCKS), replace=False))
+    rows = wire[:nb * b].view(nb, b)[torch.from_numpy(pick).to(dev)]
+    save("wire_sample", torch.cat([rows, wire[total - b:].view(1, b)]).to(torch.float32))
+
+    if "out_off" in w:
+        n = w["out_off"].numel()
+        pick = torch.from_numpy(np.sort(rng.choice(n, size=min(n, DUMP_ENTRIES), replace=False))).to(dev)
+        save("out_off_sample", w["out_off"][pick].to(torch.float64))
+        save("out_len_sample", w["out_len"][pick].to(torch.float32))
 
 
 def main():
@@ -336,12 +399,13 @@ def main():
             torch.cuda.synchronize()
 
     def measure(w, workload, warmup):
-        """Timed deobfuscate and obfuscate passes of one workload, after the warm load:
-        the line's fields.  The deobfuscate pass reads the wire the warm-up obfuscate
-        steps wrote."""
+        """The timed obfuscate pass of one workload, after the warm load: the line's
+        fields.  --full times the deobfuscate pass before it (it reads the wire the
+        warm-up obfuscate steps wrote) and looks up the PMC traffic of both."""
         w["obf"]()
         warm_load(w)
-        wall_deobf, _, ev_deobf = timed(w["deobf"], args.steps, warmup)
+        if args.full:
+            wall_deobf, _, ev_deobf = timed(w["deobf"], args.steps, warmup)
         wall_obf, mine_obf, ev_obf = timed(w["obf"], args.steps, warmup)
         total_payload = w["payload"] * world * args.steps   # every step processes the whole batch
         achieved = w["obf_bytes"] / ev_obf / 1e9
@@ -349,20 +413,22 @@ def main():
                 "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None, "kernel": KERNEL_NAMES[workload].get(w["kernel"], w["kernel"]),
                 "algorithmic_bytes_per_launch": w["obf_bytes"], "avg_launch_ms": round(ev_obf * 1e3, 4),
                 "kernel_src_sha": kernel_src_sha(), "lib_build_id": hy.build_id()}
-        t = pmc_traffic(workload, "obfuscate", w["n"], w["len"], w["kernel"])
-        if t:
-            roof["traffic"] = t["hbm_bytes_per_launch"]
-            roof["traffic_over_algorithmic"] = round(t["hbm_bytes_per_launch"] / w["obf_bytes"], 4)
-            roof["traffic_source"] = t.get("source")
-        deob = {"value": round(total_payload / wall_deobf / 2**30, 2), "unit": "GiB/s",
-                "ms_per_step": round(wall_deobf / args.steps * 1e3, 4),
-                "achieved_GBs": round(w["deobf_bytes"] / ev_deobf / 1e9, 1),
-                "frac": round(w["deobf_bytes"] / ev_deobf / 1e9 / HBM_PEAK_GBS, 4),
-                "avg_launch_ms": round(ev_deobf * 1e3, 4), "algorithmic_bytes_per_launch": w["deobf_bytes"]}
-        t = pmc_traffic(workload, "deobfuscate", w["n"], w["len"], w["kernel"])
-        if t:
-            deob["traffic"] = t["hbm_bytes_per_launch"]
-            deob["traffic_over_algorithmic"] = round(t["hbm_bytes_per_launch"] / w["deobf_bytes"], 4)
+        deob = None
+        if args.full:
+            t = pmc_traffic(workload, "obfuscate", w["n"], w["len"], w["kernel"])
+            if t:
+                roof["traffic"] = t["hbm_bytes_per_launch"]
+                roof["traffic_over_algorithmic"] = round(t["hbm_bytes_per_launch"] / w["obf_bytes"], 4)
+                roof["traffic_source"] = t.get("source")
+            deob = {"value": round(total_payload / wall_deobf / 2**30, 2), "unit": "GiB/s",
+                    "ms_per_step": round(wall_deobf / args.steps * 1e3, 4),
+                    "achieved_GBs": round(w["deobf_bytes"] / ev_deobf / 1e9, 1),
+                    "frac": round(w["deobf_bytes"] / ev_deobf / 1e9 / HBM_PEAK_GBS, 4),
+                    "avg_launch_ms": round(ev_deobf * 1e3, 4), "algorithmic_bytes_per_launch": w["deobf_bytes"]}
+            t = pmc_traffic(workload, "deobfuscate", w["n"], w["len"], w["kernel"])
+            if t:
+                deob["traffic"] = t["hbm_bytes_per_launch"]
+                deob["traffic_over_algorithmic"] = round(t["hbm_bytes_per_launch"] / w["deobf_bytes"], 4)
         per_gpu = [round(w["payload"] * args.steps / x / 2**30, 2) for x in allgather(mine_obf)]
         launch_ms = [round(x * 1e3, 4) for x in allgather(ev_obf)]
         return dict(value=total_payload / wall_obf / 2**30, ms=wall_obf / args.steps * 1e3, roofline=roof,
@@ -386,8 +452,12 @@ def main():
     torch.cuda.synchronize()
     m = measure(w, args.workload, args.warmup)
 
+    if args.dump_outputs:
+        torch.cuda.synchronize()
+        dump_outputs(w, args.dump_outputs, f"_rank{rank}" if world > 1 else "")
+
     parity = None
-    if rank == 0 and not args.no_parity:
+    if args.full and rank == 0 and not args.no_parity:
         torch.cuda.synchronize()
         parity = {"roundtrip_identity": bool(torch.equal(w["back"][:w["payload"]], w["inp"][:w["payload"]]))}
         if args.workload == "uniform" and P == (1 << 20) and L == 1200 and first == 0:
@@ -404,6 +474,7 @@ def main():
         "steps": args.steps,
         "warmup": args.warmup,
         "warm_load_ms": args.warm_load_ms,
+        "full": args.full,
         "ms_per_step": round(m["ms"], 4),
         "higher_is_better": True,
         "scaling": "weak",
@@ -420,7 +491,7 @@ def main():
     }
 
     # configs[2] beside the headline (N = 1 only): the ragged mix with packed output
-    if world == 1 and args.workload == "uniform" and not args.no_bimodal:
+    if args.full and world == 1 and args.workload == "uniform" and not args.no_bimodal:
         torch.cuda.empty_cache()
         wb = setup_bimodal(hy, obfs, dev, 1 << 22, 0)
         torch.cuda.synchronize()
@@ -438,7 +509,7 @@ def main():
                           "warmup": bw, "parity": {"roundtrip_identity": rt}}
         del wb
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(1200, args.cpu_seconds)
     elif rank == 0:
         res["cpu_baseline"] = None

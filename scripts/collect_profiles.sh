@@ -21,5 +21,5 @@ for wl in uniform bimodal uniform8m; do   # uniform8m: the N > 1 shard (bench.py
 done
 # 2. kernel trace + stats of the bench command itself
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -o run -- \
-  python3 "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-parity > "$O/kt_bench.log" 2>&1 || { echo "kt failed"; exit 1; }
+  python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity > "$O/kt_bench.log" 2>&1 || { echo "kt failed"; exit 1; }
 echo collected

@@ -8,7 +8,7 @@
 #   test            the whole GPU suite (pytest -m gpu)
 #   test:EXPR       GPU tests matching -k EXPR
 #   smoke           __graft_entry__.smoke()
-#   bench           bench.py (the driver's default line)
+#   bench           bench.py --full (the whole line: headline, deobfuscate, configs[2], cpu_baseline)
 #   trace           rocprofv3 --kernel-trace of the bench command (per-dispatch CSV + stats)
 #   collect         PMC traffic + kernel-trace stats (scripts/collect_profiles.sh TAG)
 #   aux             (f)-row rates (scripts/aux_bench.py)
@@ -18,7 +18,7 @@
 #                   library main or ab_builds/libhyobfs_LIB.so
 #   clk:WL:K:PT     per-dispatch GPU clock: rocprofv3 --pmc GRBM_COUNT GRBM_GUI_ACTIVE --kernel-trace
 #                   of scripts/prof_one.py WL K (PT=1: output buffers pre-touched); scripts/clock_trace.py
-#   clkbench:W      the same counters over the bench command (bench.py --steps 20 --warmup W)
+#   clkbench:W      the same counters over the bench command (bench.py --full --steps 20 --warmup W)
 #   kt:WL:K         rocprofv3 --kernel-trace --stats of scripts/prof_one.py WL K (per-kernel times)
 #   udp:M:P:T:W[:R] tools/udp_bench M P 4 1200 1024 T W R (loopback PacketConn rate; M = batch|raw|coalesce|single;
 #                   R = offered datagrams/s, 0 or absent = saturated)
@@ -51,9 +51,9 @@ for s in "$@"; do
     test:*) step test 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread \
             -k "${s#test:}" > "$O/pytest_gpu_k.log" 2>&1 ;;
     smoke) step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 ;;
-    bench) step bench 300 python -u bench.py > "$O/bench.json" 2> "$O/bench.err" ;;
+    bench) step bench 300 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.err" ;;
     trace) (cd /tmp && export TMPDIR=/tmp && step trace 300 rocprofv3 --kernel-trace --stats --output-format csv \
-            -d "$O/trace" -o run -- python3 "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline --no-parity \
+            -d "$O/trace" -o run -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity \
             > "$O/trace.log" 2>&1) || exit 1 ;;
     collect) step collect 1200 bash scripts/collect_profiles.sh "$TAG" > "$O/collect.log" 2>&1 ;;
     aux) step aux 300 python -u scripts/aux_bench.py > "$O/aux_bench.json" 2> "$O/aux_bench.err" ;;
@@ -74,7 +74,7 @@ for s in "$@"; do
     clkbench:*) IFS=: read -r _ W <<< "$s"   # the bench command itself, W warmup steps
             (cd /tmp && export TMPDIR=/tmp && step "clkbench $W" 240 rocprofv3 \
               --pmc GRBM_COUNT GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$O/clkbench_$W" -o run -- \
-              python3 "$R/bench.py" --steps 20 --warmup "$W" --no-cpu-baseline --no-parity > "$O/clkbench_$W.log" 2>&1) || exit 1 ;;
+              python3 "$R/bench.py" --full --steps 20 --warmup "$W" --no-cpu-baseline --no-parity > "$O/clkbench_$W.log" 2>&1) || exit 1 ;;
     kt:*) IFS=: read -r _ WL K <<< "$s"
             (cd /tmp && export TMPDIR=/tmp && step "kt $WL $K" 240 rocprofv3 --kernel-trace --stats --output-format csv \
               -d "$O/kt_${WL}_$K" -o run -- python3 "$R/scripts/prof_one.py" "$WL" "$K" > "$O/kt_${WL}_$K.log" 2>&1) || exit 1 ;;
