@@ -66,14 +66,133 @@ def test_read_crypto_payload_batch_vs_oracle(dev):
     caps = np.full(len(pkts), 2048, np.uint32)
     caps[[i for i, x in enumerate(pkts) if x[0] == "zero_prefix"][:1]] = 1089   # one byte short: -51
     out_off = np.concatenate([[0], np.cumsum(caps[:-1], dtype=np.uint64)]).astype(np.uint64)
-    d_out = torch.zeros(int(caps.sum()) + 64, dtype=torch.uint8, device=dev)
+    d_out = torch.full((int(caps.sum()) + 64,), qc.SENTINEL, dtype=torch.uint8, device=dev)
     d_res = torch.zeros(len(pkts) * 24, dtype=torch.uint8, device=dev)
     ws = torch.empty(quic.workspace_size(len(pkts)), dtype=torch.uint8, device=dev)
     quic.read_crypto_payload_batch(_t(dev, buf), _t(dev, off), _t(dev, lens), len(pkts), d_out, _t(dev, out_off),
                                    _t(dev, caps), d_res, ws)
     out = d_out.cpu().numpy()
     qc.check_crypto(pkts, out, out_off, caps, _res(d_res))
-    assert not out[int(caps.sum()):].any()
+    # the sentinel everywhere outside the data of the OK packets: the zero prefix
+    # is the kernel's own, and nothing lands in a failed packet's slot or past out_len
+    qc.check_crypto_out(pkts, out, out_off, caps, _res(d_res))
+
+
+def _unprotect_gapped(dev, cases):
+    """unprotect_batch over pack_gapped(cases): (buffer after, off, records)."""
+    from hysteria_amd import quic
+    buf, off, lens = qc.pack_gapped([c[2] for c in cases])
+    keys = np.frombuffer(b"".join(qc.key_record(c[1]) for c in cases), np.uint8).copy()
+    d_buf = _t(dev, buf)
+    d_res = torch.zeros(len(cases) * 24, dtype=torch.uint8, device=dev)
+    quic.unprotect_batch(d_buf, _t(dev, off), _t(dev, lens), len(cases), _t(dev, keys),
+                         _t(dev, np.array([c[3] for c in cases], np.int64)), d_res,
+                         pn_max=_t(dev, np.array([c[4] for c in cases], np.int64)))
+    return d_buf.cpu().numpy(), off, _res(d_res)
+
+
+def test_unprotect_lane_split_edges(dev):
+    """GHASH / Poly1305 with m = 62..66, 126..130, 192, 193 blocks over the 64
+    lanes, each suite x header shape x fill of the last block, with tampered
+    twins; the whole buffer (header, plaintext, tag, gaps) against the oracle."""
+    cases = qc.lane_split_cases()
+    qc.check_unprotect_buffer(cases, *_unprotect_gapped(dev, cases))
+
+
+def test_unprotect_pn_decode_edges(dev):
+    """decodePacketNumber at its half-window edges, pn_max = -1 and the 2^62 - win
+    guard: each packet authenticates only under the oracle's packet number.  One
+    record names a suite the kernel does not know (-53, packet untouched)."""
+    cases = qc.pn_decode_cases()
+    cases.insert(len(cases) // 2, qc.bad_suite_case())
+    qc.check_unprotect_buffer(cases, *_unprotect_gapped(dev, cases))
+
+
+def test_read_crypto_payload_edges(dev):
+    """Client Initials at the edges of the key schedule's SHA-256 padding, the
+    lane-strided frame loops, the padding ballot and the 64-byte parse window:
+    out (sentinel outside the data), the records and the packet buffer."""
+    from hysteria_amd import quic
+    pkts = qc.initial_edge_packets()
+    n, cap = len(pkts), 1536
+    buf, off, lens = qc.pack_gapped([p for _, p in pkts])
+    caps = np.full(n, cap, np.uint32)
+    out_off = np.arange(n, dtype=np.uint64) * np.uint64(cap + 32)
+    d_buf = _t(dev, buf)
+    d_out = torch.full((n * (cap + 32),), qc.SENTINEL, dtype=torch.uint8, device=dev)
+    d_res = torch.zeros(n * 24, dtype=torch.uint8, device=dev)
+    ws = torch.empty(quic.workspace_size(n), dtype=torch.uint8, device=dev)
+    quic.read_crypto_payload_batch(d_buf, _t(dev, off), _t(dev, lens), n, d_out, _t(dev, out_off), _t(dev, caps),
+                                   d_res, ws)
+    qc.check_crypto_out(pkts, d_out.cpu().numpy(), out_off, caps, _res(d_res))
+    qc.check_initial_buffer(pkts, d_buf.cpu().numpy(), off)
+
+
+def _slots(rows, width):
+    """bytes rows -> uint8[len(rows), width], padded with the sentinel."""
+    a = np.full((len(rows), width), qc.SENTINEL, np.uint8)
+    for i, r in enumerate(rows):
+        a[i, :len(r)] = np.frombuffer(r, np.uint8)
+    return a
+
+
+def _assert_rows(got, want, pick, what):
+    if not np.array_equal(got, want):
+        i = int(np.nonzero((got != want).reshape(len(pick), -1).any(axis=1))[0][0])
+        raise AssertionError((what, "packet", i, "template", int(pick[i]), "trip", i // qc.GRID_CAP))
+
+
+def test_unprotect_grid_stride_reuse(dev):
+    """More packets than the grid has blocks: blocks 0..4095 take a second packet,
+    of another suite or status class than their first, with the LDS round keys,
+    GHASH tables and the early `continue` of the first trip behind them.  Every
+    packet's slot and record equal its template's by the oracle."""
+    from hysteria_amd import quic
+    cases, classes = qc.unprotect_templates()
+    exp = [qc.expected_unprotect(*c[1:]) for c in cases]
+    n = qc.GRID_CAP + 4096
+    pick = qc.grid_stride_pick(classes, n, 31)
+    t_pkt, t_want = _slots([c[2] for c in cases], qc.SLOT), _slots([e[4] for e in exp], qc.SLOT)
+    t_key = np.frombuffer(b"".join(qc.key_record(c[1]) for c in cases), np.uint8).reshape(len(cases), 80)
+    d_buf = _t(dev, t_pkt[pick].reshape(-1))
+    d_res = torch.zeros(n * 24, dtype=torch.uint8, device=dev)
+    quic.unprotect_batch(d_buf, _t(dev, np.arange(n, dtype=np.uint64) * np.uint64(qc.SLOT)),
+                         _t(dev, np.array([len(c[2]) for c in cases], np.uint32)[pick]), n,
+                         _t(dev, t_key[pick].reshape(-1)), _t(dev, np.array([c[3] for c in cases], np.int64)[pick]),
+                         d_res, pn_max=_t(dev, np.array([c[4] for c in cases], np.int64)[pick]))
+    res = _res(d_res)
+    ok = np.array([e[0] == 0 for e in exp])[pick]
+    for f, j in (("status", 0), ("plain_len", 2)):
+        _assert_rows(res[f], np.array([e[j] for e in exp])[pick], pick, f)
+    for f, j in (("hdr_len", 1), ("pn", 3)):
+        _assert_rows(res[f][ok], np.array([e[j] for e in exp])[pick][ok], pick[ok], f)
+    _assert_rows(d_buf.cpu().numpy().reshape(n, qc.SLOT), t_want[pick], pick, "buffer")
+
+
+def test_read_crypto_payload_grid_stride_reuse(dev):
+    """The same for ReadCryptoPayload: the second trip of a block reuses the frame
+    table and the sort order in LDS after a packet of another status or frame
+    count.  out holds 64-byte capacities in 96-byte sentinel slots."""
+    from hysteria_amd import quic
+    pkts, classes = qc.initial_templates()
+    exp = [qc.expected_initial(p) for _, p in pkts]
+    n, cap, slot = qc.GRID_CAP + 4096, 64, 96
+    pick = qc.grid_stride_pick(classes, n, 32)
+    t_pkt, t_want = _slots([p for _, p in pkts], qc.SLOT), _slots([e[3] for e in exp], qc.SLOT)
+    t_out = _slots([e[1] if e[0] == 0 else b"" for e in exp], slot)
+    d_buf = _t(dev, t_pkt[pick].reshape(-1))
+    d_out = torch.full((n * slot,), qc.SENTINEL, dtype=torch.uint8, device=dev)
+    d_res = torch.zeros(n * 24, dtype=torch.uint8, device=dev)
+    ws = torch.empty(quic.workspace_size(n), dtype=torch.uint8, device=dev)
+    quic.read_crypto_payload_batch(d_buf, _t(dev, np.arange(n, dtype=np.uint64) * np.uint64(qc.SLOT)),
+                                   _t(dev, np.array([len(p) for _, p in pkts], np.uint32)[pick]), n, d_out,
+                                   _t(dev, np.arange(n, dtype=np.uint64) * np.uint64(slot)),
+                                   _t(dev, np.full(n, cap, np.uint32)), d_res, ws)
+    res = _res(d_res)
+    _assert_rows(res["status"], np.array([e[0] for e in exp])[pick], pick, "status")
+    _assert_rows(res["out_len"], np.array([len(e[1]) for e in exp], np.uint32)[pick], pick, "out_len")
+    _assert_rows(d_out.cpu().numpy().reshape(n, slot), t_out[pick], pick, "out")
+    _assert_rows(d_buf.cpu().numpy().reshape(n, qc.SLOT), t_want[pick], pick, "packets")
 
 
 def test_read_crypto_payload_helpers(dev):

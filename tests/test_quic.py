@@ -81,6 +81,58 @@ def test_crypto_cases_cover_every_status():
     assert {0, -40, -41, -42, -43, -44, -45, -46, -47, -48, -49, -50} <= seen
 
 
+def test_edge_lattices_cover_what_they_claim():
+    """The edge builders of tests/quic_cases.py, by the oracle alone: the GPU
+    tier relies on them to reach every lane-split edge with each suite, every
+    return of decodePacketNumber and the frame-loop edges, so a change that lets
+    suite and length alias again fails here."""
+    seen = {qc.AES: set(), qc.CHACHA: set()}
+    twins = 0
+    for case in qc.lane_split_cases():
+        name, key, pkt, pn_off, pn_max = case
+        st = qc.expected_unprotect(key, pkt, pn_off, pn_max)[0]
+        if name.endswith("flip"):
+            assert st == -46, name
+            twins += 1
+        else:
+            assert st == 0, name
+            seen[key.suite].add(qc.lane_split_m(case))
+    assert seen[qc.AES] == seen[qc.CHACHA] == set(qc.LANE_SPLIT_M)
+    assert twins >= 40
+    for suite in (qc.AES, qc.CHACHA):   # each suite ends a payload on its own block, and one short of it
+        lens = {len(c[2]) - qc.expected_unprotect(*c[1:])[1] - 16 for c in qc.lane_split_cases()
+                if c[1].suite == suite and not c[0].endswith("flip")}
+        assert {n % 64 for n in lens} >= {0, 63, 15, 16, 48, 49}
+
+    branches = {}
+    for case in qc.pn_decode_cases():
+        pn_len = qc.expected_unprotect(*case[1:])[1] - case[3]
+        branches.setdefault((pn_len, case[1].suite), set()).add(qc.pn_decode_branch(case))
+    assert branches == {(n, s): {-1, 0, 1} for n in (1, 2, 3, 4) for s in (qc.AES, qc.CHACHA)}
+    assert qc.expected_unprotect(*qc.bad_suite_case()[1:])[0] == -53
+
+    pkts = qc.initial_edge_packets()
+    sts = [qc.oracle_read(p)[0] for _, p in pkts]
+    assert set(sts) == {0, -50}
+    assert sts.count(0) >= 120
+    nf = {name: qc.expected_initial(p)[2] for name, p in pkts}
+    assert [nf[f"frames_{c}"] for c in (2, 63, 64, 65, 127, 128, 129, 255, 256, 257)] == \
+        [2, 63, 64, 65, 127, 128, 129, 255, 256, 257]
+    for name, p in pkts:
+        assert (qc.oracle_read(p)[0] == -50) == name.startswith(("gap_", "overlap_")), name
+
+    # the grid-stride templates: every class present, every packet inside its 64-byte slot
+    cases, classes = qc.unprotect_templates()
+    sts = [qc.expected_unprotect(*c[1:])[0] for c in cases]
+    assert set(sts) == {0, -45, -46, -53} and sts.count(0) == 86 and set(classes.tolist()) == set(range(6))
+    assert {c[1].suite for c, st in zip(cases, sts) if st == 0} == {qc.AES, qc.CHACHA}
+    assert max(len(c[2]) for c in cases) <= qc.SLOT - qc.GAP
+    pkts, classes = qc.initial_templates()
+    assert {qc.oracle_read(p)[0] for _, p in pkts} == {0, -42, -46, -47, -48, -50}
+    assert len(set(classes.tolist())) == 7 and max(len(p) for _, p in pkts) <= qc.SLOT - qc.GAP
+    assert max(len(qc.oracle_read(p)[1]) for _, p in pkts) <= 64   # the out_cap of the grid-stride batch
+
+
 # ------------------------------------------------------------------ host C ABI vs oracle
 def test_abi_initial_secret_and_keys():
     rng = np.random.default_rng(3)
