@@ -3,7 +3,7 @@
 The product is ``libhyobfs.so`` (gfx950 HIP kernels behind the C ABI of
 ``include/hyobfs.h``); this package is its Python host binding.
 """
-from . import gecko  # noqa: F401
+from . import gecko, sniff  # noqa: F401
 from .conn import SalamanderPacketConn, wrap_packet_conn_salamander  # noqa: F401
 from .gecko import GeckoOptions, GeckoPacketConn, wrap_packet_conn_gecko  # noqa: F401
 from .salamander import (  # noqa: F401
@@ -24,11 +24,20 @@ from .salamander import (  # noqa: F401
     synth_u64,
     workspace_size,
 )
+from .sniff import (  # noqa: F401
+    SNIFF_RESULT_DTYPE,
+    SniffError,
+    Sniffer,
+    client_hello_sni_batch,
+    quic_sniff_batch,
+    tls_record_sni_batch,
+)
 
 __all__ = [
     "SM_KEY_LEN", "SM_PSK_MIN_LEN", "SM_SALT_LEN", "UDP_BUFFER_SIZE", "PSKTooShortError",
     "SalamanderObfuscator", "device_count", "device_pci_bus_id", "new_salamander_obfuscator", "synth_bimodal_lengths",
     "synth_stream", "synth_u64", "workspace_size", "SalamanderPacketConn", "wrap_packet_conn_salamander",
     "obfuscate_batch_sharded", "deobfuscate_batch_sharded", "gecko", "GeckoOptions", "GeckoPacketConn",
-    "wrap_packet_conn_gecko", "build_id",
+    "wrap_packet_conn_gecko", "build_id", "sniff", "Sniffer", "SniffError", "SNIFF_RESULT_DTYPE",
+    "client_hello_sni_batch", "tls_record_sni_batch", "quic_sniff_batch",
 ]
