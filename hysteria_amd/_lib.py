@@ -73,8 +73,70 @@ def header_functions(path: str = HEADER_PATH) -> list[str]:
     return sorted(set(names))
 
 
+_vp, _sz, _u64, _u32, _i32, _i64 = (ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int,
+                                     ctypes.c_int64)
+_pbatch = ctypes.POINTER(HyobfsBatch)
+_SIG = {   # include/hyobfs.h, include/hyobfs_conn.h: name -> (restype, argtypes)
+    "hyobfs_abi_version": (_i32, []),
+    "hyobfs_build_id": (ctypes.c_char_p, []),
+    "hyobfs_status_string": (ctypes.c_char_p, [_i32]),
+    "hyobfs_device_count": (_i32, []),
+    "hyobfs_device_pci_bus_id": (_i32, [_i32, ctypes.c_char_p, _i32]),
+    "hyobfs_salamander_new": (_i32, [_vp, _sz, _i32, ctypes.POINTER(_vp)]),
+    "hyobfs_salamander_free": (None, [_vp]),
+    "hyobfs_salamander_device": (_i32, [_vp]),
+    "hyobfs_salamander_set_kernel": (_i32, [_vp, _i32]),
+    "hyobfs_salamander_seed": (None, [_vp, _u64]),
+    "hyobfs_salamander_next_salts": (None, [_vp, _vp, _sz]),
+    "hyobfs_salamander_key": (_i32, [_vp, _vp, _vp]),
+    "hyobfs_salamander_keys_batch": (_i32, [_vp, _vp, _vp, _u64, _vp]),
+    "hyobfs_salamander_obfuscate": (_sz, [_vp, _vp, _sz, _vp, _vp, _sz]),
+    "hyobfs_salamander_obfuscate_auto": (_sz, [_vp, _vp, _sz, _vp, _sz]),
+    "hyobfs_salamander_deobfuscate": (_sz, [_vp, _vp, _sz, _vp, _sz]),
+    "hyobfs_batch_workspace_size": (_u64, [_u64]),
+    "hyobfs_batch_workspace_bytes": (_u64, [_pbatch]),
+    "hyobfs_salamander_batch_kernel": (_i32, [_vp, _pbatch, _i32]),
+    "hyobfs_salamander_obfuscate_batch": (_i32, [_vp, _pbatch, _vp]),
+    "hyobfs_salamander_deobfuscate_batch": (_i32, [_vp, _pbatch, _vp]),
+    "hyobfs_salamander_obfuscate_batch_sharded": (_i32, [_vp, _pbatch, _i32]),
+    "hyobfs_salamander_deobfuscate_batch_sharded": (_i32, [_vp, _pbatch, _i32]),
+    "hyobfs_shard_bounds": (_i32, [_vp, _u64, _i32, _vp]),
+    "hyobfs_salamander_obfuscate_host": (_i32, [_vp, _pbatch, _u64]),
+    "hyobfs_salamander_deobfuscate_host": (_i32, [_vp, _pbatch, _u64]),
+    "hyobfs_host_alloc": (_vp, [_sz]),
+    "hyobfs_host_free": (None, [_vp]),
+    "hyobfs_conn_wrap": (_i32, [_i32, _vp, _u32, ctypes.POINTER(_vp)]),
+    "hyobfs_conn_close": (_i32, [_vp]),
+    "hyobfs_conn_free": (None, [_vp]),
+    "hyobfs_conn_read_from": (_i64, [_vp, _vp, _sz, _vp, ctypes.POINTER(_u32)]),
+    "hyobfs_conn_write_to": (_i64, [_vp, _vp, _sz, _vp, _u32]),
+    "hyobfs_conn_read_batch": (_i32, [_vp, _vp, _u32]),
+    "hyobfs_conn_write_batch": (_i32, [_vp, _vp, _u32]),
+    "hyobfs_conn_set_coalescing": (_i32, [_vp, _u32, _u32]),
+    "hyobfs_conn_flush": (_i32, [_vp]),
+    "hyobfs_conn_set_read_deadline": (_i32, [_vp, _i64]),
+    "hyobfs_conn_set_write_deadline": (_i32, [_vp, _i64]),
+    "hyobfs_conn_stats": (_i32, [_vp, ctypes.POINTER(_u64)]),
+    "hyobfs_synth_stream": (_i32, [_vp, _u64, _u64, _u64, _vp]),
+    "hyobfs_synth_u64": (_i32, [_vp, _u64, _u64, _u64, _vp]),
+    "hyobfs_synth_bimodal_lengths": (_i32, [_vp, _u64, _u64, _u64, _vp]),
+}
+
 _lib = None
 _variants = {}   # other builds loaded side by side (in-process A/B runs, scripts/ab_variants.py)
+
+
+def declare(lib: ctypes.CDLL, tag: str, table: dict) -> ctypes.CDLL:
+    """Set restype / argtypes of every function of ``table`` (name -> (restype,
+    argtypes)) on ``lib``, once per CDLL and ``tag``.  An undeclared function
+    would take its 64-bit arguments as C ints."""
+    done = lib.__dict__.setdefault("_declared", set())
+    if tag not in done:
+        for name, (res, args) in table.items():
+            f = getattr(lib, name)
+            f.restype, f.argtypes = res, args
+        done.add(tag)
+    return lib
 
 
 def load(path: str = LIB_PATH) -> ctypes.CDLL:
@@ -90,57 +152,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         raise OSError(f"{path} is missing: build it with `make -C hysteria_amd/csrc` "
                       "(or __graft_entry__.build()); there is no CPU fallback")
     lib = ctypes.CDLL(path, use_errno=True)
-    vp, sz, u64, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
-    pctx = ctypes.c_void_p
-    sig = {
-        "hyobfs_abi_version": (i32, []),
-        "hyobfs_build_id": (ctypes.c_char_p, []),
-        "hyobfs_status_string": (ctypes.c_char_p, [i32]),
-        "hyobfs_device_count": (i32, []),
-        "hyobfs_device_pci_bus_id": (i32, [i32, ctypes.c_char_p, i32]),
-        "hyobfs_salamander_new": (i32, [vp, sz, i32, ctypes.POINTER(ctypes.c_void_p)]),
-        "hyobfs_salamander_free": (None, [pctx]),
-        "hyobfs_salamander_device": (i32, [pctx]),
-        "hyobfs_salamander_set_kernel": (i32, [pctx, i32]),
-        "hyobfs_salamander_seed": (None, [pctx, u64]),
-        "hyobfs_salamander_next_salts": (None, [pctx, vp, sz]),
-        "hyobfs_salamander_key": (i32, [pctx, vp, vp]),
-        "hyobfs_salamander_keys_batch": (i32, [pctx, vp, vp, u64, vp]),
-        "hyobfs_salamander_obfuscate": (sz, [pctx, vp, sz, vp, vp, sz]),
-        "hyobfs_salamander_obfuscate_auto": (sz, [pctx, vp, sz, vp, sz]),
-        "hyobfs_salamander_deobfuscate": (sz, [pctx, vp, sz, vp, sz]),
-        "hyobfs_batch_workspace_size": (u64, [u64]),
-        "hyobfs_batch_workspace_bytes": (u64, [ctypes.POINTER(HyobfsBatch)]),
-        "hyobfs_salamander_batch_kernel": (i32, [pctx, ctypes.POINTER(HyobfsBatch), i32]),
-        "hyobfs_salamander_obfuscate_batch": (i32, [pctx, ctypes.POINTER(HyobfsBatch), vp]),
-        "hyobfs_salamander_deobfuscate_batch": (i32, [pctx, ctypes.POINTER(HyobfsBatch), vp]),
-        "hyobfs_salamander_obfuscate_batch_sharded": (i32, [vp, ctypes.POINTER(HyobfsBatch), i32]),
-        "hyobfs_salamander_deobfuscate_batch_sharded": (i32, [vp, ctypes.POINTER(HyobfsBatch), i32]),
-        "hyobfs_shard_bounds": (i32, [vp, u64, i32, vp]),
-        "hyobfs_salamander_obfuscate_host": (i32, [pctx, ctypes.POINTER(HyobfsBatch), u64]),
-        "hyobfs_salamander_deobfuscate_host": (i32, [pctx, ctypes.POINTER(HyobfsBatch), u64]),
-        "hyobfs_host_alloc": (vp, [sz]),
-        "hyobfs_host_free": (None, [vp]),
-        "hyobfs_conn_wrap": (i32, [i32, pctx, u32, ctypes.POINTER(ctypes.c_void_p)]),
-        "hyobfs_conn_close": (i32, [vp]),
-        "hyobfs_conn_free": (None, [vp]),
-        "hyobfs_conn_read_from": (ctypes.c_int64, [vp, vp, sz, vp, ctypes.POINTER(u32)]),
-        "hyobfs_conn_write_to": (ctypes.c_int64, [vp, vp, sz, vp, u32]),
-        "hyobfs_conn_read_batch": (i32, [vp, vp, u32]),
-        "hyobfs_conn_write_batch": (i32, [vp, vp, u32]),
-        "hyobfs_conn_set_coalescing": (i32, [vp, u32, u32]),
-        "hyobfs_conn_flush": (i32, [vp]),
-        "hyobfs_conn_set_read_deadline": (i32, [vp, ctypes.c_int64]),
-        "hyobfs_conn_set_write_deadline": (i32, [vp, ctypes.c_int64]),
-        "hyobfs_conn_stats": (i32, [vp, ctypes.POINTER(ctypes.c_uint64)]),
-        "hyobfs_synth_stream": (i32, [vp, u64, u64, u64, vp]),
-        "hyobfs_synth_u64": (i32, [vp, u64, u64, u64, vp]),
-        "hyobfs_synth_bimodal_lengths": (i32, [vp, u64, u64, u64, vp]),
-    }
-    for name, (res, args) in sig.items():
-        f = getattr(lib, name)
-        f.restype = res
-        f.argtypes = args
+    declare(lib, "core", _SIG)
     have = lib.hyobfs_abi_version()
     if have != ABI_VERSION:   # struct layouts and enum values differ between versions
         raise OSError(f"{path}: ABI version {have}, these bindings need {ABI_VERSION}: rebuild the library")

@@ -313,7 +313,7 @@ int run_batch(hyobfs_salamander* c, const hyobfs_batch* b, void* stream, bool ob
     }
     const hipError_t e = hyobfs::launch_salamander(obf, bp, c->kp, s);
     if (scratch && hipFreeAsync(scratch, s) != hipSuccess) return HYOBFS_ERR_HIP;   // after the launch, in stream order
-    return e == hipSuccess ? HYOBFS_OK : HYOBFS_ERR_HIP;
+    return hyobfs::hy_status(e);
 }
 
 // One batch per shard, each on its own context's stream (and device): launch all, then wait for all.
@@ -509,7 +509,7 @@ int hyobfs_device_count(void) {
 
 int hyobfs_device_pci_bus_id(int device, char* buf, int len) {
     if (!buf || len < 13 || device < 0 || device >= hyobfs_device_count()) return HYOBFS_ERR_INVALID;
-    return hipDeviceGetPCIBusId(buf, len, device) == hipSuccess ? HYOBFS_OK : HYOBFS_ERR_HIP;
+    return hyobfs::hy_status(hipDeviceGetPCIBusId(buf, len, device));
 }
 
 int hyobfs_salamander_new(const uint8_t* psk, size_t psk_len, int device, hyobfs_salamander** out) {
@@ -612,7 +612,7 @@ int gpu_queue_submit(GpuQueue* q, const hyobfs_batch* b, bool obf, int slot) {
     const int rc = run_batch(q->ctx, b, q->s, obf);
     if (rc != HYOBFS_OK) return rc;
     DeviceGuard g(q->ctx->device);
-    return hipEventRecord(q->ev[slot & 3], q->s) == hipSuccess ? HYOBFS_OK : HYOBFS_ERR_HIP;
+    return hyobfs::hy_status(hipEventRecord(q->ev[slot & 3], q->s));
 }
 
 // Waits for the slot's batch by sleeping between event queries.  hipEventSynchronize
@@ -624,7 +624,7 @@ int gpu_queue_submit(GpuQueue* q, const hyobfs_batch* b, bool obf, int slot) {
 // per batch and at most ~16 us of added latency.  HYOBFS_COALESCE_SPIN=1 spins instead.
 int gpu_queue_wait(GpuQueue* q, int slot) {
     hipEvent_t e = q->ev[slot & 3];
-    if (coalesce_spin()) return hipEventSynchronize(e) == hipSuccess ? HYOBFS_OK : HYOBFS_ERR_HIP;
+    if (coalesce_spin()) return hyobfs::hy_status(hipEventSynchronize(e));
     for (uint32_t us = 8;; us = us < 16 ? us * 2 : 16) {
         const hipError_t r = hipEventQuery(e);
         if (r == hipSuccess) return HYOBFS_OK;
@@ -685,7 +685,7 @@ int hyobfs_salamander_keys_batch(hyobfs_salamander* c, const uint64_t* salts, ui
     DeviceGuard g(c->device);
     if (!g.ok) return HYOBFS_ERR_HIP;
     hipStream_t s = static_cast<hipStream_t>(stream);   // NULL = the HIP null stream
-    return hyobfs::launch_keys(c->kp, salts, keys, n, s) == hipSuccess ? HYOBFS_OK : HYOBFS_ERR_HIP;
+    return hyobfs::hy_status(hyobfs::launch_keys(c->kp, salts, keys, n, s));
 }
 
 size_t hyobfs_salamander_obfuscate(hyobfs_salamander* c, const uint8_t* in, size_t in_len,
@@ -808,16 +808,14 @@ int hyobfs_gecko_encode_batch(hyobfs_salamander* c, const hyobfs_gecko_batch* b,
     DeviceGuard g(c->device);
     if (!g.ok) return HYOBFS_ERR_HIP;
     const hipError_t e = hyobfs::launch_gecko_encode(c->kp, *b, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? HYOBFS_OK : HYOBFS_ERR_HIP;
+    return hyobfs::hy_status(e);
 }
 
 int hyobfs_gecko_parse_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint64_t n,
                              hyobfs_gecko_parsed* out, void* stream) {
     if (n == 0) return HYOBFS_OK;
     if (!in || !in_off || !in_len || !out) return HYOBFS_ERR_INVALID;
-    return hyobfs::launch_gecko_parse(in, in_off, in_len, n, out, static_cast<hipStream_t>(stream)) == hipSuccess
-               ? HYOBFS_OK
-               : HYOBFS_ERR_HIP;
+    return hyobfs::hy_status(hyobfs::launch_gecko_parse(in, in_off, in_len, n, out, static_cast<hipStream_t>(stream)));
 }
 
 int hyobfs_salamander_obfuscate_host(hyobfs_salamander* c, const hyobfs_batch* b, uint64_t chunk) {
@@ -840,26 +838,18 @@ void hyobfs_host_free(void* p) {
 
 int hyobfs_synth_stream(uint8_t* dst, uint64_t nbytes, uint64_t seed, uint64_t start, void* stream) {
     if (!dst || (reinterpret_cast<uintptr_t>(dst) & 15)) return HYOBFS_ERR_INVALID;
-    return hyobfs::launch_synth_stream(dst, nbytes, seed, start, static_cast<hipStream_t>(stream)) ==
-                   hipSuccess
-               ? HYOBFS_OK
-               : HYOBFS_ERR_HIP;
+    return hyobfs::hy_status(hyobfs::launch_synth_stream(dst, nbytes, seed, start, static_cast<hipStream_t>(stream)));
 }
 
 int hyobfs_synth_u64(uint64_t* dst, uint64_t n, uint64_t seed, uint64_t first, void* stream) {
     if (!dst) return HYOBFS_ERR_INVALID;
-    return hyobfs::launch_synth_u64(dst, n, seed, first, static_cast<hipStream_t>(stream)) == hipSuccess
-               ? HYOBFS_OK
-               : HYOBFS_ERR_HIP;
+    return hyobfs::hy_status(hyobfs::launch_synth_u64(dst, n, seed, first, static_cast<hipStream_t>(stream)));
 }
 
 int hyobfs_synth_bimodal_lengths(uint32_t* dst, uint64_t n, uint64_t seed, uint64_t first,
                                  void* stream) {
     if (!dst) return HYOBFS_ERR_INVALID;
-    return hyobfs::launch_synth_bimodal(dst, n, seed, first, static_cast<hipStream_t>(stream)) ==
-                   hipSuccess
-               ? HYOBFS_OK
-               : HYOBFS_ERR_HIP;
+    return hyobfs::hy_status(hyobfs::launch_synth_bimodal(dst, n, seed, first, static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

@@ -12,7 +12,13 @@
 
 #include "../../include/hyobfs_gecko.h"
 
+// small functions shared by host and device code (sha256.h, quic_crypto.h)
+#define HY_HD __host__ __device__ __forceinline__
+
 namespace hyobfs {
+
+// the C ABI's status for the result of a HIP call or launch
+inline int hy_status(hipError_t e) { return e == hipSuccess ? HYOBFS_OK : HYOBFS_ERR_HIP; }
 
 // Orders one wave's LDS writes before its later LDS reads by other lanes of the
 // same wave.  A wave's LDS instructions execute in order, so this only has to

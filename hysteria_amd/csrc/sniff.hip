@@ -220,7 +220,7 @@ template <int MODE>
 inline int launch(const SniArgs& a, void* stream) {
     hipLaunchKernelGGL(sni_kernel<MODE>, dim3(grid_for(a.n)), dim3(64 * kWaves), 0, static_cast<hipStream_t>(stream),
                        a);
-    return hipGetLastError() == hipSuccess ? HYOBFS_OK : HYOBFS_ERR_HIP;
+    return hy_status(hipGetLastError());
 }
 
 static_assert(sizeof(hyobfs_sniff_result) == 16, "hyobfs_sniff_result layout");

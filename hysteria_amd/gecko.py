@@ -35,7 +35,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._dev import _ptr, _stream
+from ._lib import _i32, _i64, _sz, _u32, _u64, _vp, check
 
 FLAG_FRAGMENT = 0x80
 HEADER_LEN = 5
@@ -91,23 +92,20 @@ PARSED_DTYPE = np.dtype([("status", "<i4"), ("pad_len", "<u2"), ("msg_id", "u1")
 assert FRAME_DTYPE.itemsize == 16 and PARSED_DTYPE.itemsize == 16
 
 
+_hp = ctypes.POINTER(HyobfsGeckoHeader)
+_SIG = {   # include/hyobfs_gecko.h
+    "hyobfs_gecko_encode_frame": (_i64, [_hp, _vp, _sz, _vp, _sz]),
+    "hyobfs_gecko_decode_frame": (_i32, [_vp, _sz, _hp, ctypes.POINTER(_sz)]),
+    "hyobfs_gecko_pad_len": (_u32, [_i32, _i32, _u32, _u32]),
+    "hyobfs_gecko_workspace_size": (_u64, [_u64]),
+    "hyobfs_gecko_encode_batch": (_i32, [_vp, ctypes.POINTER(HyobfsGeckoBatch), _vp]),
+    "hyobfs_gecko_parse_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "hyobfs_gecko_random_pad_key": (_i32, [_vp, _vp]),
+}
+
+
 def _glib(lib=None):
-    lib = lib or _lib.load()
-    if not getattr(lib, "_gecko_declared", False):
-        vp, sz, u64, i32, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint32
-        hp = ctypes.POINTER(HyobfsGeckoHeader)
-        for name, res, args in (
-                ("hyobfs_gecko_encode_frame", ctypes.c_int64, [hp, vp, sz, vp, sz]),
-                ("hyobfs_gecko_decode_frame", i32, [vp, sz, hp, ctypes.POINTER(sz)]),
-                ("hyobfs_gecko_pad_len", u32, [i32, i32, u32, u32]),
-                ("hyobfs_gecko_workspace_size", u64, [u64]),
-                ("hyobfs_gecko_encode_batch", i32, [vp, ctypes.POINTER(HyobfsGeckoBatch), vp]),
-                ("hyobfs_gecko_parse_batch", i32, [vp, vp, vp, u64, vp, vp]),
-                ("hyobfs_gecko_random_pad_key", i32, [vp, vp])):
-            f = getattr(lib, name)
-            f.restype, f.argtypes = res, args
-        lib._gecko_declared = True
-    return lib
+    return _lib.declare(lib or _lib.load(), "gecko", _SIG)
 
 
 @dataclass(frozen=True)
@@ -400,7 +398,6 @@ def encode_batch(obfuscator, *, msg, frames, salts, out, out_off, pad_key: bytes
     and ignored (ABI 3: no scratch).  Padding is a keyed keystream
     (include/hyobfs_gecko.h): a fresh OS-random key per call unless pad_key and
     pad_nonce are given (reproducible output for tests)."""
-    from .salamander import _ptr, _stream
     if n is None:   # frames: 16-byte hyobfs_gecko_frame records
         n = frames.numel() * frames.element_size() // FRAME_DTYPE.itemsize if hasattr(frames, "numel") else len(frames)
     if pad_key is None or pad_nonce is None:
@@ -418,6 +415,5 @@ def encode_batch(obfuscator, *, msg, frames, salts, out, out_off, pad_key: bytes
 def parse_batch(inp, in_off, in_len, n: int, out, stream=None) -> None:
     """hyobfs_gecko_parse_batch: classify n deobfuscated device datagrams into ``out``
     (PARSED_DTYPE records, 16 bytes each)."""
-    from .salamander import _ptr, _stream
     check(_glib().hyobfs_gecko_parse_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), n, _ptr(out),
                                            _stream(stream, out)), "gecko_parse_batch")

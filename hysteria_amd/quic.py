@@ -28,6 +28,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from ._dev import _pack, _ptr, _records, _stream, _to
+from ._lib import _i32, _sz, _u32, _u64, _vp
 
 V1 = 0x1
 V2 = 0x6B3343CF
@@ -82,23 +84,19 @@ RESULT_DTYPE = np.dtype([("status", "<i4"), ("hdr_len", "<u4"), ("plain_len", "<
 assert KEY_DTYPE.itemsize == ctypes.sizeof(HyobfsQuicKey) == 80 and RESULT_DTYPE.itemsize == 24
 
 
-def _qlib():
-    lib = _lib.load()
-    if not getattr(lib, "_quic_declared", False):
-        vp, sz, u64, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
-        for name, res, args in (
-                ("hyobfs_quic_parse_initial_header", i32, [vp, sz, ctypes.POINTER(HyobfsQuicHeader)]),
-                ("hyobfs_quic_initial_secret", i32, [vp, sz, u32, i32, vp]),
-                ("hyobfs_quic_new_protection_key", i32, [ctypes.c_uint16, vp, sz, u32,
-                                                         ctypes.POINTER(HyobfsQuicKey)]),
-                ("hyobfs_quic_hkdf_expand_label", i32, [vp, sz, ctypes.c_char_p, vp, sz, vp, sz]),
-                ("hyobfs_quic_unprotect_batch", i32, [vp, vp, vp, u64, vp, u32, vp, vp, vp, vp]),
-                ("hyobfs_quic_workspace_size", u64, [u64]),
-                ("hyobfs_quic_read_crypto_payload_batch", i32, [vp, vp, vp, u64, vp, vp, vp, vp, vp, vp])):
-            f = getattr(lib, name)
-            f.restype, f.argtypes = res, args
-        lib._quic_declared = True
-    return lib
+_SIG = {   # include/hyobfs_quic.h
+    "hyobfs_quic_parse_initial_header": (_i32, [_vp, _sz, ctypes.POINTER(HyobfsQuicHeader)]),
+    "hyobfs_quic_initial_secret": (_i32, [_vp, _sz, _u32, _i32, _vp]),
+    "hyobfs_quic_new_protection_key": (_i32, [ctypes.c_uint16, _vp, _sz, _u32, ctypes.POINTER(HyobfsQuicKey)]),
+    "hyobfs_quic_hkdf_expand_label": (_i32, [_vp, _sz, ctypes.c_char_p, _vp, _sz, _vp, _sz]),
+    "hyobfs_quic_unprotect_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "hyobfs_quic_workspace_size": (_u64, [_u64]),
+    "hyobfs_quic_read_crypto_payload_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
+
+def _qlib(lib=None):
+    return _lib.declare(lib or _lib.load(), "quic", _SIG)
 
 
 def _raise(st: int, what: str) -> None:
@@ -197,7 +195,6 @@ def unprotect_batch(packets, off, lens, n: int, keys, pn_offset, res, *, key_str
                     stream=None) -> None:
     """hyobfs_quic_unprotect_batch: UnProtect n device packets in place; ``res``
     gets RESULT_DTYPE records.  Arguments are device tensors or pointers."""
-    from .salamander import _ptr, _stream
     st = _qlib().hyobfs_quic_unprotect_batch(_ptr(packets), _ptr(off), _ptr(lens), n, _ptr(keys), key_stride,
                                              _ptr(pn_offset), _ptr(pn_max), _ptr(res), _stream(stream, res))
     _lib.check(st, "quic_unprotect_batch")
@@ -207,29 +204,10 @@ def read_crypto_payload_batch(packets, off, lens, n: int, out, out_off, out_cap,
                               stream=None) -> None:
     """hyobfs_quic_read_crypto_payload_batch: ReadCryptoPayload of n device
     packets (unprotected in place), CRYPTO data to out[out_off[i], +out_cap[i])."""
-    from .salamander import _ptr, _stream
     st = _qlib().hyobfs_quic_read_crypto_payload_batch(_ptr(packets), _ptr(off), _ptr(lens), n, _ptr(out),
                                                        _ptr(out_off), _ptr(out_cap), _ptr(res), _ptr(workspace),
                                                        _stream(stream, res))
     _lib.check(st, "quic_read_crypto_payload_batch")
-
-
-def _pack(packets):
-    lens = np.array([len(p) for p in packets], np.uint32)
-    off = np.zeros(len(packets), np.uint64)
-    if len(packets) > 1:
-        np.cumsum(lens[:-1], out=off[1:])
-    buf = np.frombuffer(b"".join(bytes(p) for p in packets) + bytes(16), np.uint8).copy()
-    return buf, off, lens
-
-
-def _to(dev, a):
-    import torch
-    return torch.from_numpy(np.array(a, copy=True)).to(dev)   # writable copy (torch warns on read-only arrays)
-
-
-def _records(t, dtype):
-    return np.frombuffer(t.cpu().numpy().tobytes(), dtype)
 
 
 class PacketProtector:

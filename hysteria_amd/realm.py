@@ -25,6 +25,8 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from ._dev import _ptr, _stream
+from ._lib import _i32, _i64, _sz, _u32, _u64, _vp
 
 MAX_PUNCH_PADDING = 1024
 PUNCH_SALT_LEN = 8
@@ -51,20 +53,17 @@ class HyobfsPunchAttempt(ctypes.Structure):
 ATTEMPT_DTYPE = np.dtype([("nonce", "u1", (PUNCH_NONCE_SIZE,)), ("key", "u1", (PUNCH_OBFS_KEY_SIZE,))])
 
 
-def _rlib():
-    lib = _lib.load()
-    if not getattr(lib, "_realm_declared", False):
-        vp, sz, u64, u32, i32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
-        ap = ctypes.POINTER(HyobfsPunchAttempt)
-        for name, res, args in (
-                ("hyobfs_punch_encode", ctypes.c_int64, [ctypes.c_uint8, ap, vp, vp, sz, vp, sz]),
-                ("hyobfs_punch_decode", i32, [vp, sz, ap, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(u32)]),
-                ("hyobfs_punch_mask", None, [vp, vp, vp]),
-                ("hyobfs_punch_match_batch", i32, [vp, vp, vp, u64, vp, u32, vp, vp, vp, vp])):
-            f = getattr(lib, name)
-            f.restype, f.argtypes = res, args
-        lib._realm_declared = True
-    return lib
+_ap = ctypes.POINTER(HyobfsPunchAttempt)
+_SIG = {   # include/hyobfs_realm.h
+    "hyobfs_punch_encode": (_i64, [ctypes.c_uint8, _ap, _vp, _vp, _sz, _vp, _sz]),
+    "hyobfs_punch_decode": (_i32, [_vp, _sz, _ap, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(_u32)]),
+    "hyobfs_punch_mask": (None, [_vp, _vp, _vp]),
+    "hyobfs_punch_match_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
+}
+
+
+def _rlib(lib=None):
+    return _lib.declare(lib or _lib.load(), "realm", _SIG)
 
 
 @dataclass(frozen=True)
@@ -162,7 +161,6 @@ class PunchMatcher:
                     stream=None) -> None:
         """match[i] = first attempt index datagram i decodes under, or -1 (device tensors).
         ``attempts``: the device copy of ``self.attempts`` (uint8 tensor) -- made by the caller."""
-        from .salamander import _ptr, _stream
         _lib.check(_rlib().hyobfs_punch_match_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), n, _ptr(attempts),
                                                     len(self.metas), _ptr(match), _ptr(ptype), _ptr(padding),
                                                     _stream(stream, match)), "punch_match_batch")

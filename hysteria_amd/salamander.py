@@ -22,6 +22,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _lib
+from ._dev import _hptr, _ptr, _stream
 from ._lib import HyobfsBatch, check
 
 SM_PSK_MIN_LEN = 4    # salamander.go:14
@@ -54,36 +55,6 @@ def _cbuf(b, writable=False):
         return ctypes.addressof(buf), n, buf
     arr = (ctypes.c_char * n).from_buffer(mv)
     return ctypes.addressof(arr), n, (arr, mv)
-
-
-def _ptr(x):
-    """Device pointer of a torch tensor / int / None."""
-    if x is None:
-        return None
-    if isinstance(x, int):
-        return x
-    return x.data_ptr()
-
-
-def _hptr(x):
-    """Host pointer of a numpy array / CPU torch tensor / int / None."""
-    if x is None:
-        return None
-    if isinstance(x, int):
-        return x
-    if hasattr(x, "data_ptr"):
-        return x.data_ptr()
-    return x.ctypes.data
-
-
-def _stream(stream, *tensors):
-    if stream is not None:
-        return stream if isinstance(stream, int) else stream.cuda_stream
-    for t in tensors:
-        if t is not None and not isinstance(t, int) and getattr(t, "is_cuda", False):
-            import torch
-            return torch.cuda.current_stream(t.device).cuda_stream
-    return None
 
 
 def _make_batch(*, inp, n, in_off=None, in_stride=0, in_len=None, len_uniform=0, salts=None, out,

@@ -27,13 +27,14 @@ sniff.go:109-127).
 """
 from __future__ import annotations
 
-import ctypes
 import ipaddress
 import re
 
 import numpy as np
 
 from . import _lib, quic
+from ._dev import _pack, _ptr, _records, _stream, _to
+from ._lib import _i32, _u32, _u64, _vp
 
 MAX_EXTENSIONS = 256
 MAX_NAME_LEN = 255   # a DNS name on the wire; the default name_stride
@@ -62,19 +63,16 @@ SNIFF_RESULT_DTYPE = np.dtype([("status", "<i4"), ("name_len", "<u4"), ("name_of
 assert SNIFF_RESULT_DTYPE.itemsize == 16
 
 
-def _slib():
-    lib = quic._qlib()
-    if not getattr(lib, "_sniff_declared", False):
-        vp, u64, u32, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
-        for name, res, args in (
-                ("hyobfs_tls_client_hello_sni_batch", i32, [vp, vp, vp, u64, vp, u32, vp, vp]),
-                ("hyobfs_tls_record_sni_batch", i32, [vp, vp, vp, u64, vp, u32, vp, vp]),
-                ("hyobfs_quic_sniff_workspace_size", u64, [u64]),
-                ("hyobfs_quic_sniff_batch", i32, [vp, vp, vp, u64, vp, vp, vp, vp, vp, u32, vp, vp, vp])):
-            f = getattr(lib, name)
-            f.restype, f.argtypes = res, args
-        lib._sniff_declared = True
-    return lib
+_SIG = {   # include/hyobfs_sniff.h
+    "hyobfs_tls_client_hello_sni_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp]),
+    "hyobfs_tls_record_sni_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp]),
+    "hyobfs_quic_sniff_workspace_size": (_u64, [_u64]),
+    "hyobfs_quic_sniff_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+}
+
+
+def _slib(lib=None):
+    return _lib.declare(quic._qlib(lib), "sniff", _SIG)   # quic_snis also reads quic's results
 
 
 # ------------------------------------------------------------------ device batches
@@ -82,7 +80,6 @@ def client_hello_sni_batch(msgs, off, lens, n: int, names, name_stride: int, res
     """hyobfs_tls_client_hello_sni_batch: the server name of n device-resident
     ClientHello messages to names[i * name_stride, +name_len); ``res`` gets
     SNIFF_RESULT_DTYPE records.  Arguments are device tensors or pointers."""
-    from .salamander import _ptr, _stream
     st = _slib().hyobfs_tls_client_hello_sni_batch(_ptr(msgs), _ptr(off), _ptr(lens), n, _ptr(names), name_stride,
                                                    _ptr(res), _stream(stream, res))
     _lib.check(st, "tls_client_hello_sni_batch")
@@ -91,7 +88,6 @@ def client_hello_sni_batch(msgs, off, lens, n: int, names, name_stride: int, res
 def tls_record_sni_batch(msgs, off, lens, n: int, names, name_stride: int, res, stream=None) -> None:
     """hyobfs_tls_record_sni_batch: the same over the first bytes of n TCP
     streams (isTLS, the record length, then the record's body)."""
-    from .salamander import _ptr, _stream
     st = _slib().hyobfs_tls_record_sni_batch(_ptr(msgs), _ptr(off), _ptr(lens), n, _ptr(names), name_stride,
                                              _ptr(res), _stream(stream, res))
     _lib.check(st, "tls_record_sni_batch")
@@ -105,7 +101,6 @@ def quic_sniff_batch(packets, off, lens, n: int, crypto, crypto_off, crypto_cap,
                      sres, workspace, stream=None) -> None:
     """hyobfs_quic_sniff_batch: read_crypto_payload_batch (in place; ``qres`` and
     ``crypto`` as that call leaves them), then the server name of every payload."""
-    from .salamander import _ptr, _stream
     st = _slib().hyobfs_quic_sniff_batch(_ptr(packets), _ptr(off), _ptr(lens), n, _ptr(crypto), _ptr(crypto_off),
                                          _ptr(crypto_cap), _ptr(qres), _ptr(names), name_stride, _ptr(sres),
                                          _ptr(workspace), _stream(stream, sres))
@@ -129,11 +124,11 @@ def _sni_many(call, msgs, device, name_stride):
     n = len(msgs)
     if n == 0:
         return []
-    buf, off, lens = quic._pack(msgs)
+    buf, off, lens = _pack(msgs)
     d_names = torch.zeros(n * name_stride, dtype=torch.uint8, device=dev)
     d_res = torch.zeros(n * SNIFF_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    call(quic._to(dev, buf), quic._to(dev, off), quic._to(dev, lens), n, d_names, name_stride, d_res)
-    return _names(quic._records(d_res, SNIFF_RESULT_DTYPE), d_names.cpu().numpy(), name_stride)
+    call(_to(dev, buf), _to(dev, off), _to(dev, lens), n, d_names, name_stride, d_res)
+    return _names(_records(d_res, SNIFF_RESULT_DTYPE), d_names.cpu().numpy(), name_stride)
 
 
 def client_hello_snis(msgs, device: int = 0, name_stride: int = MAX_NAME_LEN):
@@ -155,17 +150,17 @@ def quic_snis(packets, device: int = 0, crypto_cap: int = 4096, name_stride: int
     n = len(packets)
     if n == 0:
         return []
-    buf, off, lens = quic._pack(packets)
+    buf, off, lens = _pack(packets)
     d_crypto = torch.zeros(n * crypto_cap, dtype=torch.uint8, device=dev)
     d_qres = torch.zeros(n * quic.RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
     d_names = torch.zeros(n * name_stride, dtype=torch.uint8, device=dev)
     d_sres = torch.zeros(n * SNIFF_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
     ws = torch.empty(max(quic_sniff_workspace_size(n), 1), dtype=torch.uint8, device=dev)
-    quic_sniff_batch(quic._to(dev, buf), quic._to(dev, off), quic._to(dev, lens), n, d_crypto,
-                     quic._to(dev, np.arange(n, dtype=np.uint64) * np.uint64(crypto_cap)),
-                     quic._to(dev, np.full(n, crypto_cap, np.uint32)), d_qres, d_names, name_stride, d_sres, ws)
-    out = _names(quic._records(d_sres, SNIFF_RESULT_DTYPE), d_names.cpu().numpy(), name_stride)
-    qres = quic._records(d_qres, quic.RESULT_DTYPE)
+    quic_sniff_batch(_to(dev, buf), _to(dev, off), _to(dev, lens), n, d_crypto,
+                     _to(dev, np.arange(n, dtype=np.uint64) * np.uint64(crypto_cap)),
+                     _to(dev, np.full(n, crypto_cap, np.uint32)), d_qres, d_names, name_stride, d_sres, ws)
+    out = _names(_records(d_sres, SNIFF_RESULT_DTYPE), d_names.cpu().numpy(), name_stride)
+    qres = _records(d_qres, quic.RESULT_DTYPE)
     big = [i for i in range(n) if qres[i]["status"] == quic.ERR_OUT_CAP]
     if big and crypto_cap < quic.MAX_CRYPTO_PAYLOAD_LEN:
         again = quic_snis([packets[i] for i in big], device, max(quic.MAX_CRYPTO_PAYLOAD_LEN,

@@ -24,6 +24,18 @@ def test_library_exports_every_header_symbol():
     assert set(names) <= exported
 
 
+def test_every_header_function_is_declared():
+    """A function whose argtypes were never set takes its 64-bit arguments as C ints."""
+    from hysteria_amd import gecko, quic, realm, sniff
+    libs = [gecko._glib(), realm._rlib(), quic._qlib(), sniff._slib()]
+    lib = _lib.load()
+    assert all(x is lib for x in libs)
+    names = _lib.header_functions()
+    assert len(names) >= 65
+    undeclared = [n for n in names if getattr(lib, n).argtypes is None]
+    assert not undeclared, undeclared
+
+
 def test_abi_basics():
     lib = _lib.load()
     assert lib.hyobfs_abi_version() == _lib.ABI_VERSION == 4

@@ -106,8 +106,9 @@ def sniff_main():
         pytest.skip("no host clang for the emulated build")
     csrc = os.path.join(ROOT, "hysteria_amd", "csrc")
     srcs = [os.path.join(EMU, "sniff_main.cpp"), os.path.join(csrc, "sniff.hip"), os.path.join(csrc, "quic.hip")]
-    deps = srcs + [os.path.join(EMU, "hip_emu.h"), os.path.join(csrc, "kernels.h"),
-                   os.path.join(ROOT, "include", "hyobfs_sniff.h"), os.path.join(ROOT, "include", "hyobfs_quic.h")]
+    deps = srcs + [os.path.join(EMU, "hip_emu.h"), os.path.join(csrc, "kernels.h"), os.path.join(csrc, "sha256.h"),
+                   os.path.join(csrc, "quic_crypto.h"), os.path.join(ROOT, "include", "hyobfs_sniff.h"),
+                   os.path.join(ROOT, "include", "hyobfs_quic.h")]
     os.makedirs(os.path.join(EMU, "build"), exist_ok=True)
     exe = os.path.join(EMU, "build", "sniff_main")
     with open(os.path.join(EMU, "build", ".sniff_main.lock"), "w") as lk:
