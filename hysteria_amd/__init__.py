@@ -3,7 +3,17 @@
 The product is ``libhyobfs.so`` (gfx950 HIP kernels behind the C ABI of
 ``include/hyobfs.h``); this package is its Python host binding.
 """
-from . import gecko, sniff  # noqa: F401
+from . import acl, gecko, sniff  # noqa: F401
+from .acl import (  # noqa: F401
+    ACL_RESULT_DTYPE,
+    CompilationError,
+    InvalidSyntaxError,
+    RuleSet,
+    TextRule,
+    compile_rules,
+    parse_text_rules,
+    quic_sniff_and_match,
+)
 from .conn import SalamanderPacketConn, wrap_packet_conn_salamander  # noqa: F401
 from .gecko import GeckoOptions, GeckoPacketConn, wrap_packet_conn_gecko  # noqa: F401
 from .salamander import (  # noqa: F401
@@ -39,5 +49,6 @@ __all__ = [
     "synth_stream", "synth_u64", "workspace_size", "SalamanderPacketConn", "wrap_packet_conn_salamander",
     "obfuscate_batch_sharded", "deobfuscate_batch_sharded", "gecko", "GeckoOptions", "GeckoPacketConn",
     "wrap_packet_conn_gecko", "build_id", "sniff", "Sniffer", "SniffError", "SNIFF_RESULT_DTYPE",
-    "client_hello_sni_batch", "tls_record_sni_batch", "quic_sniff_batch",
+    "client_hello_sni_batch", "tls_record_sni_batch", "quic_sniff_batch", "acl", "ACL_RESULT_DTYPE", "CompilationError",
+    "InvalidSyntaxError", "RuleSet", "TextRule", "compile_rules", "parse_text_rules", "quic_sniff_and_match",
 ]

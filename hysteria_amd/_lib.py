@@ -122,6 +122,16 @@ _SIG = {   # include/hyobfs.h, include/hyobfs_conn.h: name -> (restype, argtypes
     "hyobfs_synth_bimodal_lengths": (_i32, [_vp, _u64, _u64, _u64, _vp]),
 }
 
+_ACL_SIG = {   # include/hyobfs_acl.h (hysteria_amd/acl.py, which imports the sniffer's bindings and so cannot be
+    # imported by them): load() declares these with the core table
+    "hyobfs_acl_ruleset_new": (_i32, [_vp, _u32, _i32, ctypes.POINTER(_vp)]),
+    "hyobfs_acl_ruleset_free": (None, [_vp]),
+    "hyobfs_acl_ruleset_rules": (_u32, [_vp]),
+    "hyobfs_acl_ruleset_bad_rule": (_i64, []),
+    "hyobfs_acl_match_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "hyobfs_acl_match_sniffed_batch": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+}
+
 _lib = None
 _variants = {}   # other builds loaded side by side (in-process A/B runs, scripts/ab_variants.py)
 
@@ -153,6 +163,10 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
                       "(or __graft_entry__.build()); there is no CPU fallback")
     lib = ctypes.CDLL(path, use_errno=True)
     declare(lib, "core", _SIG)
+    # a build without acl.hip (the emulated library of tests/emu/build.sh) still loads for what it
+    # has; acl._alib() declares the table unconditionally, so using the ACL with such a build fails there
+    if hasattr(lib, "hyobfs_acl_ruleset_new"):
+        declare(lib, "acl", _ACL_SIG)
     have = lib.hyobfs_abi_version()
     if have != ABI_VERSION:   # struct layouts and enum values differ between versions
         raise OSError(f"{path}: ABI version {have}, these bindings need {ABI_VERSION}: rebuild the library")
