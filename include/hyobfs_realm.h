@@ -67,9 +67,14 @@ void hyobfs_punch_mask(const uint8_t key[32], const uint8_t salt[8], uint8_t mas
  * decodePunchPacket over a batch (punch_conn.go:146-165), on the current
  * device: datagram i is in[in_off[i], +in_len[i]); attempts[0..m) on the
  * device.  match[i] = the lowest attempt index the datagram decodes under,
- * or -1; type[i] and padding[i] describe that match.  (The reference walks a
- * map, so which of several matching attempts wins is unspecified there; a
- * real collision needs a SHA-256 prefix collision.)  Asynchronous on stream.
+ * or -1; type[i] and padding[i] describe that match, and both are 0 on a
+ * miss (match[i] == -1), whatever the datagram's bytes or length.  type and
+ * padding may be NULL; attempts may be NULL when m == 0 (every datagram
+ * misses).  Only the first 33 wire bytes of a datagram are read, and none of
+ * a datagram whose length is out of range; n == 0 writes nothing.  (The
+ * reference walks a map, so which of several matching attempts wins is
+ * unspecified there; a real collision needs a SHA-256 prefix collision.)
+ * Asynchronous on stream.
  */
 int hyobfs_punch_match_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint64_t n,
                              const hyobfs_punch_attempt* attempts, uint32_t m, int32_t* match, uint8_t* type,

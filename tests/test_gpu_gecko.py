@@ -11,6 +11,8 @@ import pytest
 from oracle import gecko_ref as gref
 from oracle import salamander_ref as sref
 
+import wire_cases as wc
+
 pytestmark = pytest.mark.gpu
 PSK = b"average_password"
 KEY, NONCE = bytes(range(7, 39)), bytes(range(100, 112))   # explicit pad keystream key: reproducible wire
@@ -365,3 +367,111 @@ def test_encode_random_pad_key_padding_is_keystream(gpu):
     exp = d.size / 256
     chi2 = float(((counts - exp) ** 2 / exp).sum())
     assert d.size > 100_000 and chi2 < 400, (d.size, chi2)   # 255 dof: mean 255, sd ~22.6
+
+
+# ---------------------------------------------------------------- the edge lattices (tests/wire_cases.py)
+def test_parse_lattice_all_fields(gpu):
+    """len 0..8 x first byte x every idx_total x pad lengths around the padding check,
+    and two 2040-byte datagrams: all six fields of every record (zero but `status`
+    for EMPTY and the errors), an input buffer that ends with its last datagram, 64
+    guard bytes around `parsed`."""
+    import torch
+    from hysteria_amd import gecko
+    lat = wc.parse_lattice()
+    n = len(lat["len"])
+    assert wc.PARSED_DTYPE == gecko.PARSED_DTYPE
+    guarded = torch.full((64 + 16 * n + 64,), wc.SENTINEL, dtype=torch.uint8, device=gpu)
+    gecko.parse_batch(_dev(lat["buf"], gpu), _dev(lat["off"], gpu).view(torch.int64),
+                      _dev(lat["len"], gpu).view(torch.int32), n, guarded[64:64 + 16 * n])
+    torch.cuda.synchronize()
+    h = guarded.cpu().numpy()
+    assert (h[:64] == wc.SENTINEL).all() and (h[64 + 16 * n:] == wc.SENTINEL).all()
+    got = h[64:64 + 16 * n].view(gecko.PARSED_DTYPE)
+    bad = np.flatnonzero(got != lat["exp"])
+    assert bad.size == 0, (bad.size, int(bad[0]), int(lat["len"][bad[0]]), got[bad[0]], lat["exp"][bad[0]])
+
+
+def _encode_into(gpu, cs, out):
+    """One encode call of a wire_cases case: tensors of exactly the case's sizes."""
+    import hysteria_amd
+    from hysteria_amd import gecko
+    o = hysteria_amd.SalamanderObfuscator(cs["psk"], 0)
+    try:
+        gecko.encode_batch(o, msg=_dev(cs["msg"], gpu), frames=_dev(cs["frames"], gpu), salts=_dev(cs["salts"], gpu),
+                           pad_key=wc.PAD_KEY, pad_nonce=wc.PAD_NONCE, out=out, out_off=_dev(cs["off"], gpu),
+                           n=len(cs["frames"]))
+        import torch
+        torch.cuda.synchronize()
+    finally:
+        o.close()
+
+
+@pytest.mark.parametrize("order", wc.ENCODE_ORDERS)
+@pytest.mark.parametrize("mode", wc.ENCODE_MODES)
+def test_encode_layout_lattice(gpu, mode, order):
+    """Chunks of 0..19 / 0..1499 bytes and wire datagrams of 2046..2050, n around one
+    and two wave groups, skipped frames anywhere (a group's first frame included),
+    chunks ending at msg's last byte, four PSK lengths: the whole `out`, byte for
+    byte, the sentinel wherever no valid frame lies; msg and out without slack."""
+    import torch
+    cases = [cs for cs in wc.encode_cases() if (cs["mode"], cs["order"]) == (mode, order)]
+    assert [cs["n"] for cs in cases] == list(wc.ENCODE_NS)
+    for cs in cases:
+        out = torch.full((cs["out_len"],), wc.SENTINEL, dtype=torch.uint8, device=gpu)
+        _encode_into(gpu, cs, out)
+        got = out.cpu().numpy()
+        bad = np.flatnonzero(got != cs["exp"])
+        assert bad.size == 0, (cs["name"], bad.size, int(bad[0]))
+
+
+def _check_far(gpu, big, cs):
+    """A far-offset case into the real buffer `big`: only the windows (the frames and
+    100 sentinel bytes on either side) are filled before and copied back after."""
+    assert cs["hi"] <= big.numel()
+    for a, e in cs["windows"]:
+        big[a:a + len(e)] = wc.SENTINEL
+    _encode_into(gpu, cs, big)
+    for a, e in cs["windows"]:
+        got = big[a:a + len(e)].cpu().numpy()
+        bad = np.flatnonzero(got != e)
+        assert bad.size == 0, (cs["name"], a, bad.size, int(bad[0]))
+
+
+def test_encode_and_punch_offsets_past_4GiB(gpu):
+    """One buffer of 2^32 + 64 KiB: frames straddling out_off = 2^32 in ascending and
+    in shuffled placement, an ascending group whose second half lies 2^32 + 5 bytes
+    on (the window path: 32-bit group-relative offsets cannot hold it), and punch
+    datagrams whose in_off lie past 2^32."""
+    import torch
+    from hysteria_amd import realm
+    big = torch.empty((1 << 32) + (64 << 10), dtype=torch.uint8, device=gpu)
+    far = wc.far_cases()
+    for name in ("straddle32_ascending", "straddle32_shuffled", "span32_window"):
+        _check_far(gpu, big, far[name])
+    lat = wc.punch_lattice()
+    n, base = 257, (1 << 32) + 16
+    assert base + len(lat["buf"]) <= big.numel()
+    big[base:base + len(lat["buf"])] = _dev(lat["buf"], gpu)
+    off = np.where(lat["real"][:n] == 1, lat["off"][:n] + np.uint64(base), np.uint64(big.numel()))
+    mt = realm.PunchMatcher([realm.PunchMetadata(nonce.hex(), key.hex()) for nonce, key in lat["attempts"]])
+    match = torch.full((n,), -7, dtype=torch.int32, device=gpu)
+    ty = torch.full((n,), 0xEE, dtype=torch.uint8, device=gpu)
+    pad = torch.full((n,), -7, dtype=torch.int32, device=gpu)
+    mt.match_batch(big, _dev(off.astype(np.uint64), gpu), _dev(lat["len"][:n], gpu), n, match, ty, pad,
+                   attempts=_dev(mt.attempts, gpu))
+    torch.cuda.synchronize()
+    got = list(zip(match.cpu().tolist(), ty.cpu().tolist(), pad.cpu().tolist()))
+    assert got == wc.punch_expected(n, 5)
+    assert sum(j >= 0 for j, _, _ in got) > 40
+
+
+def test_encode_group_wire_span_2GiB(gpu):
+    """One buffer of 2^31 + 64 KiB: an ascending 40-frame group with a jump of
+    2^31 - 2000 bytes in its middle (its wire span stays under 2^31: the aligned sweep)
+    and the same with a jump of 2^31 + 5 (the span reaches 2^31: the window path);
+    span31_aligned runs on this tier only, so the CPU tier's 2^24 jump runs here too."""
+    import torch
+    big = torch.empty((1 << 31) + (64 << 10), dtype=torch.uint8, device=gpu)
+    far = wc.far_cases()
+    for name in ("span31_aligned", "span31_window", "span24_aligned"):
+        _check_far(gpu, big, far[name])
