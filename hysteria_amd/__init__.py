@@ -39,7 +39,9 @@ from .sniff import (  # noqa: F401
     SniffError,
     Sniffer,
     client_hello_sni_batch,
+    http_request_host_batch,
     quic_sniff_batch,
+    tcp_sniff_batch,
     tls_record_sni_batch,
 )
 
@@ -51,4 +53,5 @@ __all__ = [
     "wrap_packet_conn_gecko", "build_id", "sniff", "Sniffer", "SniffError", "SNIFF_RESULT_DTYPE",
     "client_hello_sni_batch", "tls_record_sni_batch", "quic_sniff_batch", "acl", "ACL_RESULT_DTYPE", "CompilationError",
     "InvalidSyntaxError", "RuleSet", "TextRule", "compile_rules", "parse_text_rules", "quic_sniff_and_match",
+    "http_request_host_batch", "tcp_sniff_batch",
 ]

@@ -17,10 +17,16 @@
 //                same LDS byte.  The types of the extensions seen
 //                so far are a per-wave list in LDS, searched 64 entries per
 //                step and a ballot.  The name is copied a byte per lane.
+//   tcp_kernel   the first bytes of a TCP stream, by Sniffer.TCP's dispatch
+//                (sniff.go:103-156), with the same shape: a wave looks at its
+//                stream's first three bytes and runs the HTTP scan of
+//                sniff_http.h or the record front end and the walk above.
+//                With HTTP_ONLY it is the HTTP branch alone.
 // Waves of a workgroup share nothing and never meet at a barrier, so a wave
 // whose message fails at byte 0 does not wait for a neighbour's 256 extensions.
 #include "kernels.h"
 #include "../../include/hyobfs_sniff.h"
+#include "sniff_http.h"
 
 namespace hyobfs {
 namespace sniff {
@@ -211,6 +217,50 @@ __global__ __launch_bounds__(64 * kWaves) void sni_kernel(SniArgs a) {
     }
 }
 
+// Sniffer.TCP over the first bytes of a stream: isHTTP, else isTLS, else
+// unrecognised (HTTP_ONLY: the HTTP branch alone, NOT_HTTP otherwise).
+template <bool HTTP_ONLY>
+__global__ __launch_bounds__(64 * kWaves) void tcp_kernel(SniArgs a) {
+    __shared__ uint16_t seen_all[kWaves][HTTP_ONLY ? 1 : HYOBFS_TLS_MAX_EXTENSIONS];
+    static_assert(kStage >= kHttpStage, "the HTTP scan stages in the same LDS bytes");
+    __shared__ uint8_t stage_all[kWaves][kStage];
+    // the wave's number as a scalar, so that m, the stream's length and address and every loop over them are scalar
+    const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for (uint64_t m = (uint64_t)blockIdx.x * kWaves + wave; m < a.n; m += (uint64_t)gridDim.x * kWaves) {
+        const uint32_t L = a.len[m];
+        const uint8_t* p = a.msgs + a.off[m];
+        HttpParsed r = http_parse(p, L, stage_all[wave], lane);
+        if (!HTTP_ONLY && r.status == HYOBFS_SNIFF_ERR_NOT_HTTP) {
+            if (L < 3) {
+                r = HttpParsed{HYOBFS_SNIFF_ERR_NEED_MORE, 0, 0, 3};
+            } else if (uni(p[0]) < 0x16 || uni(p[0]) > 0x17 || uni(p[1]) != 0x03 || uni(p[2]) > 0x09) {   // isTLS, :59-65
+                r.status = HYOBFS_SNIFF_ERR_UNRECOGNIZED;
+            } else {                                                                  // sniff.go:128-143
+                Window w{p, L, 0, stage_all[wave]};
+                w.fill(0, lane);
+                const uint32_t need = L < 5 ? 5 : 5 + w.u16(3, lane);
+                if (L < need) {
+                    r = HttpParsed{HYOBFS_SNIFF_ERR_NEED_MORE, 0, 0, need};
+                } else {
+                    const Parsed t = parse_client_hello(w, 5, need, seen_all[wave], lane);
+                    r = HttpParsed{t.status, t.name_off, t.name_len, 0};   // both 0 unless OK
+                }
+            }
+        }
+        hyobfs_sniff_result out{r.status, r.name_len, r.name_off, r.need};
+        if (r.status == HYOBFS_OK && r.name_len) {
+            if (r.name_len > a.name_stride) {
+                out.status = HYOBFS_SNIFF_ERR_NAME_CAP;
+            } else {
+                uint8_t* d = a.names + m * a.name_stride;
+                const uint8_t* s = p + r.name_off;
+                for (uint32_t q = lane; q < r.name_len; q += 64) d[q] = s[q];
+            }
+        }
+        if (lane == 0) a.res[m] = out;
+    }
+}
+
 inline uint32_t grid_for(uint64_t n) {
     const uint64_t g = (n + kWaves - 1) / kWaves;
     return (uint32_t)(g < kGridCap ? g : kGridCap);
@@ -220,6 +270,13 @@ template <int MODE>
 inline int launch(const SniArgs& a, void* stream) {
     hipLaunchKernelGGL(sni_kernel<MODE>, dim3(grid_for(a.n)), dim3(64 * kWaves), 0, static_cast<hipStream_t>(stream),
                        a);
+    return hy_status(hipGetLastError());
+}
+
+template <bool HTTP_ONLY>
+inline int launch_tcp(const SniArgs& a, void* stream) {
+    hipLaunchKernelGGL(tcp_kernel<HTTP_ONLY>, dim3(grid_for(a.n)), dim3(64 * kWaves), 0,
+                       static_cast<hipStream_t>(stream), a);
     return hy_status(hipGetLastError());
 }
 
@@ -245,6 +302,20 @@ int hyobfs_tls_record_sni_batch(const uint8_t* msgs, const uint64_t* off, const 
     if (n == 0) return HYOBFS_OK;
     if (!msgs || !off || !len || !names || !res) return HYOBFS_ERR_INVALID;
     return launch<kRecord>(SniArgs{msgs, off, len, nullptr, n, names, name_stride, res}, stream);
+}
+
+int hyobfs_http_request_host_batch(const uint8_t* msgs, const uint64_t* off, const uint32_t* len, uint64_t n,
+                                   uint8_t* names, uint32_t name_stride, hyobfs_sniff_result* res, void* stream) {
+    if (n == 0) return HYOBFS_OK;
+    if (!msgs || !off || !len || !names || !res) return HYOBFS_ERR_INVALID;
+    return launch_tcp<true>(SniArgs{msgs, off, len, nullptr, n, names, name_stride, res}, stream);
+}
+
+int hyobfs_tcp_sniff_batch(const uint8_t* msgs, const uint64_t* off, const uint32_t* len, uint64_t n, uint8_t* names,
+                           uint32_t name_stride, hyobfs_sniff_result* res, void* stream) {
+    if (n == 0) return HYOBFS_OK;
+    if (!msgs || !off || !len || !names || !res) return HYOBFS_ERR_INVALID;
+    return launch_tcp<false>(SniArgs{msgs, off, len, nullptr, n, names, name_stride, res}, stream);
 }
 
 uint64_t hyobfs_quic_sniff_workspace_size(uint64_t n) { return hyobfs_quic_workspace_size(n); }

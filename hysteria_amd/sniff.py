@@ -1,4 +1,4 @@
-"""The protocol sniffer's TLS / QUIC server-name extraction -- ``extras/sniff/sniff.go`` on MI355X.
+"""The protocol sniffer: TLS / QUIC server names and HTTP request hosts -- ``extras/sniff/sniff.go`` on MI355X.
 
 ==================================================  ==================================================
 reference (Go)                                      here
@@ -8,6 +8,9 @@ UDPPorts}`` (sniff.go:31-36)                        udp_ports)``
 ``(*Sniffer).Check`` (:67-89)                       ``Sniffer.check(is_udp, req_addr)``
 ``(*Sniffer).UDP`` (:159-174)                       ``Sniffer.udp_many(datagrams, req_addrs)`` and
                                                     ``quic_sniff_batch`` (GPU, many packets)
+``(*Sniffer).TCP`` (:91-157)                        ``Sniffer.tcp_many(stream_prefixes, req_addrs)`` and
+                                                    ``tcp_sniff_batch`` (GPU)
+``(*Sniffer).TCP``, the HTTP branch (:110-127)      ``http_request_host_batch`` (GPU)
 ``(*Sniffer).TCP``, the TLS branch (:128-144)       ``Sniffer.tls_many(stream_prefixes, req_addrs)`` and
                                                     ``tls_record_sni_batch`` (GPU)
 ``utls.UnmarshalClientHello(pl).ServerName``        ``client_hello_sni_batch`` (GPU)
@@ -15,15 +18,19 @@ UDPPorts}`` (sniff.go:31-36)                        udp_ports)``
 ==================================================  ==================================================
 
 The parse runs in ``libhyobfs.so`` (``include/hyobfs_sniff.h`` states its rules
-and the one divergence from the reference's parser); there is no CPU path.
+and the divergences from the reference's parsers); there is no CPU path.
 ``Sniffer`` works on whole batches: a caller collects the first datagram (or the
 first stream bytes) of many new connections and gets every rewritten request
 address back from one call.  Reading from a stream under ``timeout`` is the
 caller's; a prefix that does not yet hold the whole record leaves its address
 unchanged, as the reference does when its deadline passes.
 
-Out of scope: the HTTP branch of ``Sniffer.TCP`` (Go's ``http.ReadRequest``,
-sniff.go:109-127).
+The HTTP branch answers ``ERR_HOST`` ("left to the host") for the rarer request
+forms whose answer the library leaves to the caller's own ``http.ReadRequest``
+(an absolute-form or CONNECT target, folded header lines, Transfer-Encoding,
+Trailer, an odd Content-Length, a Host value with an empty host part).  This
+mirror has no ``net/http``: ``Sniffer.tcp_many`` keeps such an item's address
+unchanged, where the reference might rewrite it.
 """
 from __future__ import annotations
 
@@ -38,6 +45,7 @@ from ._lib import _i32, _u32, _u64, _vp
 
 MAX_EXTENSIONS = 256
 MAX_NAME_LEN = 255   # a DNS name on the wire; the default name_stride
+MAX_HTTP_HEADER_BYTES = 256 * 1024   # sniffMaxHTTPHeaderBytes (sniff.go:21): what the HTTP branch reads of a stream
 
 ERRORS = {
     -54: "not a client hello",
@@ -47,9 +55,13 @@ ERRORS = {
     -58: "not a TLS record",
     -59: "record not complete yet",
     -60: "no crypto payload",
+    -65: "not an HTTP request",
+    -66: "request left to the host's parser",
+    -67: "neither HTTP nor TLS",
 }
 ERR_NOT_HELLO, ERR_MALFORMED, ERR_NAME_CAP, ERR_EXTENSIONS, ERR_NOT_TLS, ERR_NEED_MORE, ERR_NO_PAYLOAD = \
     range(-54, -61, -1)
+ERR_NOT_HTTP, ERR_HOST, ERR_UNRECOGNIZED = -65, -66, -67   # -61 .. -64 are the ACL's
 
 
 class SniffError(ValueError):
@@ -66,6 +78,8 @@ assert SNIFF_RESULT_DTYPE.itemsize == 16
 _SIG = {   # include/hyobfs_sniff.h
     "hyobfs_tls_client_hello_sni_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp]),
     "hyobfs_tls_record_sni_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp]),
+    "hyobfs_http_request_host_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp]),
+    "hyobfs_tcp_sniff_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp]),
     "hyobfs_quic_sniff_workspace_size": (_u64, [_u64]),
     "hyobfs_quic_sniff_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
 }
@@ -91,6 +105,22 @@ def tls_record_sni_batch(msgs, off, lens, n: int, names, name_stride: int, res, 
     st = _slib().hyobfs_tls_record_sni_batch(_ptr(msgs), _ptr(off), _ptr(lens), n, _ptr(names), name_stride,
                                              _ptr(res), _stream(stream, res))
     _lib.check(st, "tls_record_sni_batch")
+
+
+def http_request_host_batch(msgs, off, lens, n: int, names, name_stride: int, res, stream=None) -> None:
+    """hyobfs_http_request_host_batch: the host part of the Host header of n TCP
+    stream prefixes (isHTTP, then rules H0-H7 of include/hyobfs_sniff.h)."""
+    st = _slib().hyobfs_http_request_host_batch(_ptr(msgs), _ptr(off), _ptr(lens), n, _ptr(names), name_stride,
+                                                _ptr(res), _stream(stream, res))
+    _lib.check(st, "http_request_host_batch")
+
+
+def tcp_sniff_batch(msgs, off, lens, n: int, names, name_stride: int, res, stream=None) -> None:
+    """hyobfs_tcp_sniff_batch: Sniffer.TCP's dispatch over n TCP stream prefixes
+    in one launch (HTTP, else TLS, else ERR_UNRECOGNIZED)."""
+    st = _slib().hyobfs_tcp_sniff_batch(_ptr(msgs), _ptr(off), _ptr(lens), n, _ptr(names), name_stride,
+                                        _ptr(res), _stream(stream, res))
+    _lib.check(st, "tcp_sniff_batch")
 
 
 def quic_sniff_workspace_size(n: int) -> int:
@@ -139,6 +169,17 @@ def client_hello_snis(msgs, device: int = 0, name_stride: int = MAX_NAME_LEN):
 def tls_record_snis(prefixes, device: int = 0, name_stride: int = MAX_NAME_LEN):
     """Server names of a list of TCP stream prefixes on cuda:<device>: bytes or a SniffError each."""
     return _sni_many(tls_record_sni_batch, prefixes, device, name_stride)
+
+
+def http_request_hosts(prefixes, device: int = 0, name_stride: int = MAX_NAME_LEN):
+    """Request hosts of a list of TCP stream prefixes on cuda:<device>: bytes or a SniffError each."""
+    return _sni_many(http_request_host_batch, prefixes, device, name_stride)
+
+
+def tcp_snis(prefixes, device: int = 0, name_stride: int = MAX_NAME_LEN):
+    """What Sniffer.TCP finds in a list of TCP stream prefixes on cuda:<device>
+    (an HTTP request's host or a ClientHello's server name): bytes or a SniffError each."""
+    return _sni_many(tcp_sniff_batch, prefixes, device, name_stride)
 
 
 def quic_snis(packets, device: int = 0, crypto_cap: int = 4096, name_stride: int = MAX_NAME_LEN):
@@ -265,3 +306,10 @@ class Sniffer:
     def tls_many(self, stream_prefixes, req_addrs, device: int = 0) -> list[str]:
         """Check, then the TLS branch of TCP (sniff.go:128-152), per stream prefix."""
         return self._many(False, tls_record_snis, stream_prefixes, req_addrs, device)
+
+    def tcp_many(self, stream_prefixes, req_addrs, device: int = 0) -> list[str]:
+        """Check, then TCP (sniff.go:91-157), per stream prefix: the request address,
+        rewritten to an HTTP request's host or a ClientHello's server name where
+        there is one.  An item the library leaves to the host (ERR_HOST) keeps its
+        address: this mirror has no http.ReadRequest to fall back on."""
+        return self._many(False, lambda items, device: tcp_snis(items, device), stream_prefixes, req_addrs, device)
