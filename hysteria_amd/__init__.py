@@ -17,6 +17,7 @@ from .acl import (  # noqa: F401
 from .conn import SalamanderPacketConn, wrap_packet_conn_salamander  # noqa: F401
 from .gecko import GeckoOptions, GeckoPacketConn, wrap_packet_conn_gecko  # noqa: F401
 from .salamander import (  # noqa: F401
+    BATCH_MAX_DATAGRAM,
     SM_KEY_LEN,
     SM_PSK_MIN_LEN,
     SM_SALT_LEN,
@@ -53,5 +54,5 @@ __all__ = [
     "wrap_packet_conn_gecko", "build_id", "sniff", "Sniffer", "SniffError", "SNIFF_RESULT_DTYPE",
     "client_hello_sni_batch", "tls_record_sni_batch", "quic_sniff_batch", "acl", "ACL_RESULT_DTYPE", "CompilationError",
     "InvalidSyntaxError", "RuleSet", "TextRule", "compile_rules", "parse_text_rules", "quic_sniff_and_match",
-    "http_request_host_batch", "tcp_sniff_batch",
+    "http_request_host_batch", "tcp_sniff_batch", "BATCH_MAX_DATAGRAM",
 ]

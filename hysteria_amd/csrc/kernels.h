@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../../include/hyobfs.h"
 #include "../../include/hyobfs_gecko.h"
 
 // small functions shared by host and device code (sha256.h, quic_crypto.h)
@@ -35,7 +36,8 @@ __device__ __forceinline__ void hy_wave_sync() {
 #endif
 
 constexpr int kTile = 256;          // datagrams per tile-sum entry of the packed layout's scan
-constexpr uint32_t kMaxDatagram = (1u << 24) - 64;  // longest datagram a batch accepts
+constexpr uint32_t kMaxDatagram = HYOBFS_BATCH_MAX_DATAGRAM;   // longest datagram a call accepts (include/hyobfs.h)
+static_assert(kMaxDatagram == (1u << 24) - 64, "the wave kernel's 32-bit virtual offsets assume 64 datagrams < 2^30");
 constexpr uint64_t kMaxStride = 1ull << 24;         // longest slot of a slotted output
 // batch kernels (include/hyobfs.h HYOBFS_KERNEL_*)
 constexpr int kKernelAuto = 0, kKernelWave = 1, kKernelTile = 2, kKernelFlat = 3;

@@ -81,7 +81,9 @@ struct FlatParams {
     // it, ~0 = none): [0] its output offset = the end of the valid output, [1] its index
     uint64_t* cut;
     uint64_t ntiles_max;
-    const uint64_t* in_total;    // input bytes: the length scan's total (device)
+    // readable input bytes (device): the length scan's total, lowered by flat_locate_kernel to
+    // the offset of the first datagram over kMaxDatagram (dropped: its input is not read)
+    uint64_t* in_total;
     const uint64_t* out_total;   // the width scan's total: the valid output's end without a cut
     uint8_t* krec;      // key records: per datagram 4 granules {key word, epoch} (krec_*)
     uint64_t epoch;     // this call's tag (never 0)
@@ -190,6 +192,16 @@ __global__ __launch_bounds__(256) void flat_locate_kernel(BatchParams B, FlatPar
             } else if (W[k] && cut == ~0ull) {
                 cut = p;
                 cut_o = o;
+            }
+        }
+        // a datagram over the limit has no input to read: the staged windows end in front of it
+        if (L[k] > kMaxDatagram) {   // *in_total = min(*in_total, i)
+            unsigned long long* const tot = reinterpret_cast<unsigned long long*>(F.in_total);
+            unsigned long long cur = atomicAdd(tot, 0ull);
+            while (cur > i) {
+                const unsigned long long seen = atomicCAS(tot, cur, (unsigned long long)i);
+                if (seen == cur) break;
+                cur = seen;
             }
         }
         o += W[k];
@@ -375,7 +387,7 @@ __device__ __forceinline__ void flat_hasher(const BatchParams& B, const KeyParam
             }
             const uint32_t L = live ? B.in_len[k] : 0u;
             const uint64_t i = B.in_tile_prefix[g] + wave_sum(pre) + wave_incl_scan32(L, (int)lane) - L;
-            if (L > 8u) salt = load8u(B.in + i);
+            if (out_width<false>(L, B.pkt_cap)) salt = load8u(B.in + i);   // a dropped datagram's input is not read
         }
         uint64_t key[4];
         wave_key<SW>(K, salt, key);

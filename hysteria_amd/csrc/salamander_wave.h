@@ -71,6 +71,10 @@ struct GroupBufT {                   // one wave's group, in LDS (4736 B with 64
     uint16_t park[kGroup];           // bits 0-2 parked (first, second, last chunk), 3-5 late, 8-15 first slot
 };
 static_assert(HY_PACKED_PARK_SLOTS >= kGroup && HY_PACKED_PARK_SLOTS <= 255, "park slot index is 8 bits");
+// a wave's virtual offsets are 32-bit: 64 regions of at most kMaxDatagram + 8 bytes (slotted: of at most
+// kMaxStride), each run padded to a 128-byte line, plus the sweep's last step
+static_assert((uint64_t)kGroup * (kMaxStride + 8 + 256) + 16ull * kGroup * HY_WU < (1ull << 31),
+              "the wave kernel's virtual layout needs 32-bit headroom");
 
 // ---- BLAKE2b message words of the device block(s).  The message is
 // PSK || salt, zero padded: every word after the salt's is a compile-time 0,

@@ -29,6 +29,9 @@ SM_PSK_MIN_LEN = 4    # salamander.go:14
 SM_SALT_LEN = 8       # salamander.go:15
 SM_KEY_LEN = 32       # salamander.go:16
 UDP_BUFFER_SIZE = 2048  # conn.go:10
+# HYOBFS_BATCH_MAX_DATAGRAM (include/hyobfs.h): the longest datagram any call accepts; a longer one
+# is dropped like an invalid one (per-packet calls return 0, a batch reports out_len 0 for it)
+BATCH_MAX_DATAGRAM = (1 << 24) - 64
 
 
 class PSKTooShortError(ValueError):

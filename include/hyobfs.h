@@ -93,6 +93,12 @@ extern "C" {
 #define HYOBFS_SALT_LEN 8     /* smSaltLen,   salamander.go:15 */
 #define HYOBFS_KEY_LEN 32     /* smKeyLen,    salamander.go:16 */
 #define HYOBFS_UDP_BUFFER_SIZE 2048 /* udpBufferSize, conn.go:10 */
+/* Longest datagram (input bytes L) any call accepts: this library's limit, not the
+   reference's (Go slices have no such bound).  A longer datagram is dropped like
+   an invalid one: a per-packet call returns 0; in a batch its out_len is 0, its
+   input is not read and packed offsets do not move for it.  A slotted batch's
+   out_stride above it is HYOBFS_ERR_INVALID. */
+#define HYOBFS_BATCH_MAX_DATAGRAM ((1u << 24) - 64)
 
 /* status codes (negative = error) */
 #define HYOBFS_OK 0
@@ -168,7 +174,8 @@ int hyobfs_salamander_key(hyobfs_salamander* ctx, const uint8_t salt[8],
    Device pointers, enqueued on stream (a hipStream_t; NULL = the null stream). */
 int hyobfs_salamander_keys_batch(hyobfs_salamander* ctx, const uint64_t* salts,
                                  uint8_t* keys, uint64_t n, void* stream);
-/* Obfuscate (salamander.go:59-72) with an explicit salt.  Host buffers, synchronous. */
+/* Obfuscate (salamander.go:59-72) with an explicit salt.  Host buffers, synchronous.
+   The per-packet calls return 0 for in_len > HYOBFS_BATCH_MAX_DATAGRAM. */
 size_t hyobfs_salamander_obfuscate(hyobfs_salamander* ctx, const uint8_t* in,
                                    size_t in_len, const uint8_t salt[8],
                                    uint8_t* out, size_t out_len);
@@ -194,10 +201,14 @@ size_t hyobfs_salamander_deobfuscate(hyobfs_salamander* ctx, const uint8_t* in,
  *   salt    : obfuscate only: salts[i], 8 bytes, little-endian u64
  *             (salt byte b = (salts[i] >> 8b) & 0xff)
  *   output  : W_i = L_i + 8 (obfuscate) or L_i - 8 (deobfuscate)
- *             valid iff W_i > 0 and W_i <= cap_i, where cap_i = pkt_cap
- *             (0 = unlimited), further limited to out_stride when slotted
- *             (that is `len(out)` of the per-packet call)
+ *             valid iff L_i <= HYOBFS_BATCH_MAX_DATAGRAM, W_i > 0 and W_i <= cap_i,
+ *             where cap_i = pkt_cap (0 = unlimited), further limited to
+ *             out_stride when slotted (that is `len(out)` of the per-packet
+ *             call).  An invalid datagram is dropped: out_len 0, its input is
+ *             not read, and it takes no room in a packed output.
  *   layout  : out_stride > 0  -> slotted: out_off_i = i * out_stride
+ *                                (out_stride > HYOBFS_BATCH_MAX_DATAGRAM:
+ *                                HYOBFS_ERR_INVALID, nothing runs)
  *             out_stride == 0 -> packed : out_off_i = exclusive prefix sum of
  *                                the valid W's (the datagrams sit back to back)
  *             a packet whose region passes out_cap is dropped (packed: so is

@@ -196,6 +196,8 @@ size_t oracle_salamander_deobfuscate(const uint8_t* psk, size_t psk_len,
  *   dropped too); a dropped packet writes nothing and reports out_len 0.
  * Returns the number of bytes written (sum of out_len).
  */
+#define ORACLE_BATCH_MAX_DATAGRAM ((1u << 24) - 64)
+
 static uint64_t batch_common(int obf, const uint8_t* psk, size_t psk_len,
                              uint64_t n, const uint8_t* in,
                              const uint64_t* in_off, uint64_t in_stride,
@@ -213,6 +215,10 @@ static uint64_t batch_common(int obf, const uint8_t* psk, size_t psk_len,
         if (out_stride && out_stride < cap) cap = out_stride;
         int valid = W > 0 && (uint64_t)W <= cap;
         if (!obf && W <= 0) valid = 0;
+        /* this project's limit, not the reference's (include/hyobfs.h,
+           HYOBFS_BATCH_MAX_DATAGRAM): a longer datagram is dropped like an
+           invalid one, its input is not read, packed offsets do not move */
+        if (L > ORACLE_BATCH_MAX_DATAGRAM) valid = 0;
         if (!valid) W = 0;
         uint64_t off = out_stride ? i * out_stride : cursor;
         /* packed offsets are a pure prefix sum of the per-packet rule above;

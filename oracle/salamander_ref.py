@@ -76,6 +76,53 @@ def deobfuscate(psk: bytes, wire: bytes, out_len: int | None = None) -> bytes:
     return _xor_key(wire[SM_SALT_LEN:], key(psk, wire[:SM_SALT_LEN]))
 
 
+# ------------------------------------------------------------------ batch
+# This project's limit, not the reference's (include/hyobfs.h,
+# HYOBFS_BATCH_MAX_DATAGRAM): a datagram of more input bytes is dropped like an
+# invalid one -- out_len 0, its input not read, packed offsets do not move; the
+# per-packet calls of the library return 0 for it.
+BATCH_MAX_DATAGRAM = (1 << 24) - 64
+
+
+def batch(obf: bool, psk: bytes, n: int, inp, *, in_off=None, in_stride=0, in_len=None, len_uniform=0,
+          salts=None, out_cap: int, out_stride=0, pkt_cap=0):
+    """The batch rules of include/hyobfs.h in plain Python, contiguous input included
+    (in_off None, in_stride 0, in_len given, n > 1: datagram i right after i - 1).
+
+    Returns (regions, out_off, out_len, total): regions is a list of (offset, bytes)
+    for the valid datagrams, everything else of ``out`` stays unwritten."""
+    contiguous = in_off is None and in_stride == 0 and in_len is not None and n > 1
+    cap = pkt_cap if pkt_cap else None
+    if out_stride and (cap is None or out_stride < cap):
+        cap = out_stride
+    mem = memoryview(inp)
+    regions, out_off, out_len = [], np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+    cursor = total = ipos = 0
+    for i in range(n):
+        L = int(in_len[i]) if in_len is not None else int(len_uniform)
+        src = ipos if contiguous else int(in_off[i]) if in_off is not None else i * in_stride
+        ipos += L
+        W = L + SM_SALT_LEN if obf else L - SM_SALT_LEN
+        valid = L <= BATCH_MAX_DATAGRAM and W > 0 and (cap is None or W <= cap)
+        if not valid:
+            W = 0
+        off = i * out_stride if out_stride else cursor
+        if not out_stride:
+            cursor += W          # the out_cap clip below never moves later datagrams
+        if valid and off + W > out_cap:
+            valid, W = False, 0
+        out_off[i], out_len[i] = off, W
+        if not valid:
+            continue
+        data = bytes(mem[src:src + L])
+        assert len(data) == L, "datagram %d reaches past the input buffer" % i
+        wire = obfuscate(psk, data, int(salts[i]).to_bytes(8, "little")) if obf else deobfuscate(psk, data)
+        assert len(wire) == W
+        regions.append((off, wire))
+        total += W
+    return regions, out_off, out_len, total
+
+
 # ------------------------------------------------------------------ seeded inputs
 GOLDEN = 0x9E3779B97F4A7C15
 M64 = (1 << 64) - 1
