@@ -3,7 +3,7 @@
 The product is ``libhyobfs.so`` (gfx950 HIP kernels behind the C ABI of
 ``include/hyobfs.h``); this package is its Python host binding.
 """
-from . import acl, gecko, sniff  # noqa: F401
+from . import acl, gecko, sniff, udpmsg  # noqa: F401
 from .acl import (  # noqa: F401
     ACL_RESULT_DTYPE,
     CompilationError,
@@ -46,6 +46,17 @@ from .sniff import (  # noqa: F401
     tls_record_sni_batch,
 )
 
+from .udpmsg import (  # noqa: F401
+    UDP_META_DTYPE,
+    UDP_PARSED_DTYPE,
+    Defragger,
+    UDPMessage,
+    UDPMessageError,
+    frag_udp_message,
+    parse_udp_message,
+    relay_quic_snis,
+)
+
 __all__ = [
     "SM_KEY_LEN", "SM_PSK_MIN_LEN", "SM_SALT_LEN", "UDP_BUFFER_SIZE", "PSKTooShortError",
     "SalamanderObfuscator", "device_count", "device_pci_bus_id", "new_salamander_obfuscator", "synth_bimodal_lengths",
@@ -54,5 +65,6 @@ __all__ = [
     "wrap_packet_conn_gecko", "build_id", "sniff", "Sniffer", "SniffError", "SNIFF_RESULT_DTYPE",
     "client_hello_sni_batch", "tls_record_sni_batch", "quic_sniff_batch", "acl", "ACL_RESULT_DTYPE", "CompilationError",
     "InvalidSyntaxError", "RuleSet", "TextRule", "compile_rules", "parse_text_rules", "quic_sniff_and_match",
-    "http_request_host_batch", "tcp_sniff_batch", "BATCH_MAX_DATAGRAM",
+    "http_request_host_batch", "tcp_sniff_batch", "BATCH_MAX_DATAGRAM", "udpmsg", "UDPMessage", "UDPMessageError",
+    "parse_udp_message", "frag_udp_message", "Defragger", "relay_quic_snis", "UDP_PARSED_DTYPE", "UDP_META_DTYPE",
 ]

@@ -132,6 +132,21 @@ _ACL_SIG = {   # include/hyobfs_acl.h (hysteria_amd/acl.py, which imports the sn
     "hyobfs_acl_match_sniffed_batch": (_i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),
 }
 
+_UDP_SIG = {   # include/hyobfs_udpmsg.h (hysteria_amd/udpmsg.py); declared by load() like the ACL's
+    "hyobfs_udp_header_size": (_u32, [_u32]),
+    "hyobfs_udp_serialize": (_i64, [_vp, _vp, _u32, _vp, _u32, _vp, _sz]),
+    "hyobfs_udp_parse": (_i32, [_vp, _sz, _vp]),
+    "hyobfs_udp_frag_plan": (_i32, [_u32, _u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
+    "hyobfs_udp_send_frags": (_i32, [_vp, _vp, _vp, _u32, _vp, _sz, _vp, ctypes.POINTER(_u32)]),
+    "hyobfs_udp_defragger_new": (_vp, []),
+    "hyobfs_udp_defragger_free": (None, [_vp]),
+    "hyobfs_udp_defragger_feed": (_i32, [_vp, _vp, _u64, _vp, ctypes.POINTER(_u32)]),
+    "hyobfs_udp_parse_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "hyobfs_udp_frag_workspace_size": (_u64, [_u64]),
+    "hyobfs_udp_frag_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "hyobfs_udp_assemble_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 _variants = {}   # other builds loaded side by side (in-process A/B runs, scripts/ab_variants.py)
 
@@ -167,6 +182,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     # has; acl._alib() declares the table unconditionally, so using the ACL with such a build fails there
     if hasattr(lib, "hyobfs_acl_ruleset_new"):
         declare(lib, "acl", _ACL_SIG)
+    if hasattr(lib, "hyobfs_udp_parse_batch"):   # likewise udpmsg.hip / udpmsg_host.cpp (udpmsg._ulib())
+        declare(lib, "udpmsg", _UDP_SIG)
     have = lib.hyobfs_abi_version()
     if have != ABI_VERSION:   # struct layouts and enum values differ between versions
         raise OSError(f"{path}: ABI version {have}, these bindings need {ABI_VERSION}: rebuild the library")
