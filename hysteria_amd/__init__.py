@@ -15,7 +15,7 @@ from .acl import (  # noqa: F401
     quic_sniff_and_match,
 )
 from .conn import SalamanderPacketConn, wrap_packet_conn_salamander  # noqa: F401
-from .gecko import GeckoOptions, GeckoPacketConn, wrap_packet_conn_gecko  # noqa: F401
+from .gecko import GeckoOptions, GeckoPacketConn, GeckoReceiver, wrap_packet_conn_gecko  # noqa: F401
 from .salamander import (  # noqa: F401
     BATCH_MAX_DATAGRAM,
     SM_KEY_LEN,
@@ -67,4 +67,5 @@ __all__ = [
     "InvalidSyntaxError", "RuleSet", "TextRule", "compile_rules", "parse_text_rules", "quic_sniff_and_match",
     "http_request_host_batch", "tcp_sniff_batch", "BATCH_MAX_DATAGRAM", "udpmsg", "UDPMessage", "UDPMessageError",
     "parse_udp_message", "frag_udp_message", "Defragger", "relay_quic_snis", "UDP_PARSED_DTYPE", "UDP_META_DTYPE",
+    "GeckoReceiver",
 ]

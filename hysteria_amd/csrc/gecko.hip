@@ -23,6 +23,9 @@
 //
 // Parse: one thread per deobfuscated datagram, the checks of ReadFrom
 // (gecko.go:170-193) and decodeFrame (gecko_frame.go:65-86) in their order.
+//
+// Peek and open: the receive side on the wire bytes, without the padding (the
+// comments at gecko_peek_kernel and gecko_open_kernel).
 #include "kernels.h"
 #include "salamander_device.h"
 #include "salamander_wave.h"   // wave_key<SW>: the key unrolled per salt word
@@ -568,38 +571,219 @@ __global__ __launch_bounds__(256) HY_GK_ATTR void gecko_encode_kernel(KeyParams 
     edges(emask);   // ---- 3. all edge windows after the sweep
 }
 
-__global__ __launch_bounds__(256) void gecko_parse_kernel(const uint8_t* in, const uint64_t* in_off,
-                                                          const uint32_t* in_len, uint64_t n,
-                                                          hyobfs_gecko_parsed* out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// The record of one plaintext datagram of `len` bytes whose byte j is at(j): ReadFrom's
+// classification and decodeFrame's checks in their order.  at(0) is read when len > 0,
+// at(1..4) only for a flagged datagram of at least five bytes.
+template <class ByteAt>
+__device__ __forceinline__ hyobfs_gecko_parsed gk_classify(uint32_t len, ByteAt at) {
     hyobfs_gecko_parsed r{};
-    const uint32_t len = in_len[i];
-    const uint8_t* d = in + in_off[i];
     if (len == 0) {
         r.status = HYOBFS_GECKO_EMPTY;                       // n <= 0: continue
-    } else if (!(d[0] & HYOBFS_GECKO_FLAG_FRAGMENT)) {
+    } else if (!(at(0) & HYOBFS_GECKO_FLAG_FRAGMENT)) {
         r.status = HYOBFS_GECKO_PASS;                        // short header / garbage: passed through
         r.payload_len = len;
     } else if (len < HYOBFS_GECKO_HEADER_LEN) {
         r.status = HYOBFS_GECKO_ERR_TRUNCATED;
     } else {
-        const uint32_t it = d[2], total = it & 0x0f, idx = it >> 4;
-        const uint32_t pad = ((uint32_t)d[3] << 8) | d[4];
+        const uint32_t it = at(2), total = it & 0x0f, idx = it >> 4;
+        const uint32_t pad = ((uint32_t)at(3) << 8) | at(4);
         if (total < HYOBFS_GECKO_MIN_CHUNKS || total > HYOBFS_GECKO_MAX_CHUNKS || idx >= total) {
             r.status = HYOBFS_GECKO_ERR_INVALID;
         } else if (HYOBFS_GECKO_HEADER_LEN + pad > len) {
             r.status = HYOBFS_GECKO_ERR_TRUNCATED;
         } else {
             r.status = HYOBFS_GECKO_FRAGMENT;
-            r.msg_id = d[1];
+            r.msg_id = at(1);
             r.idx_total = (uint8_t)it;
             r.pad_len = (uint16_t)pad;
             r.payload_off = HYOBFS_GECKO_HEADER_LEN + pad;
             r.payload_len = len - r.payload_off;
         }
     }
-    out[i] = r;
+    return r;
+}
+
+__global__ __launch_bounds__(256) void gecko_parse_kernel(const uint8_t* in, const uint64_t* in_off,
+                                                          const uint32_t* in_len, uint64_t n,
+                                                          hyobfs_gecko_parsed* out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* d = in + in_off[i];
+    out[i] = gk_classify(in_len[i], [&](uint32_t j) -> uint8_t { return d[j]; });
+}
+
+// ---------------------------------------------------------------- receive side, on the wire
+// Peek: one lane per wire datagram.  The key (keyLocked, salamander.go:88-91) from
+// the salt, then the record of the plaintext behind it, of which only the first
+// byte -- and for a flagged datagram of at least five bytes the next four -- is
+// read and XORed with the key's first bytes.  A datagram of at most eight bytes has
+// no plaintext (salamander.go:75-77): EMPTY, no key.
+template <int SW>
+__global__ __launch_bounds__(256) void gecko_peek_kernel(KeyParams K, const uint8_t* wire, const uint64_t* wire_off,
+                                                         const uint32_t* wire_len, uint64_t n,
+                                                         hyobfs_gecko_parsed* parsed, uint8_t* keys) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t wl = wire_len[i];
+    if (wl <= HYOBFS_SALT_LEN) {
+        hyobfs_gecko_parsed r{};
+        r.status = HYOBFS_GECKO_EMPTY;
+        parsed[i] = r;
+        return;
+    }
+    const uint8_t* w = wire + wire_off[i];
+    uint64_t kw[4];
+    wave_key<SW>(K, load8u(w), kw);
+    gk_store16u(keys + 32 * i, (gk_u128)kw[1] << 64 | kw[0]);
+    gk_store16u(keys + 32 * i + 16, (gk_u128)kw[3] << 64 | kw[2]);
+    const uint8_t* d = w + HYOBFS_SALT_LEN;
+    const uint64_t k0 = kw[0];   // key bytes 0..7: the plaintext index is the key phase (salamander.go:82-84)
+    parsed[i] = gk_classify(wl - HYOBFS_SALT_LEN, [&](uint32_t j) -> uint8_t { return d[j] ^ (uint8_t)(k0 >> (8 * j)); });
+}
+
+// Open: four messages per wave, 16 lanes each (the shape of udp_assemble_kernel,
+// udpmsg.hip).  Lane sl of a message checks the list's slot sl and holds its piece
+// (where the payload starts in `wire`, its length, its key); a 16-lane scan gives the
+// pieces' offsets in the message; the 16 lanes then sweep the message's output in
+// aligned 16-byte windows.  A window inside one piece is one unaligned 16-byte load,
+// one XOR and one aligned 16-byte store; a window that holds a seam is composed from
+// its pieces under byte masks; only the message's first and last window can be partial
+// and are stored under a byte mask.  The key of a piece is rotated once, by its lane, so
+// that the window's address selects one of its two halves (as the encoder's aligned path
+// does): window byte j at virtual address a is plaintext byte payload_off + a + j - vb -
+// pre, so the key rotated left by (vb + pre - payload_off) mod 32 is indexed by (a + j) mod 32.
+constexpr uint32_t kGkNoPiece = 0xFFFFFFFFu;
+constexpr int kGkOpenLanes = 16;                      // lanes that share a message
+constexpr int kGkOpenPerWave = 64 / kGkOpenLanes;     // messages per wave
+constexpr int kGkOpenWaves = 4;                       // waves per workgroup
+constexpr int kGkOpenU = 4;                           // windows per lane and step: a step's loads before its stores
+static_assert(HYOBFS_GECKO_MAX_CHUNKS <= kGkOpenLanes, "one lane per piece");
+
+struct GkOpenMsg {   // one message's pieces, in LDS
+    uint32_t pre[HYOBFS_GECKO_MAX_CHUNKS + 1];   // where piece q starts in the message; [count] = the total; beyond: none
+    uint64_t src[HYOBFS_GECKO_MAX_CHUNKS];       // where its payload starts in `wire`
+    gk_u128 key[2 * HYOBFS_GECKO_MAX_CHUNKS];    // its key rotated to the output's 32-byte phase, two halves
+};
+
+__device__ __forceinline__ void gk_open_sweep(const uint8_t* __restrict__ wire, uint8_t* out, uint64_t o, uint32_t total,
+                                              const GkOpenMsg& M, uint32_t sl) {
+    const uint32_t vb = (uint32_t)((reinterpret_cast<uintptr_t>(out) + o) & 15u);
+    uint8_t* const wbase = out + o - vb;   // 16-aligned
+    const uint64_t end = (uint64_t)vb + total;
+    const uint32_t nwin = (uint32_t)((end + 15u) >> 4);
+    for (uint32_t T = 0; T < nwin; T += kGkOpenLanes * kGkOpenU) {
+        gk_u128 r[kGkOpenU];
+        uint32_t cov[kGkOpenU];
+#pragma unroll
+        for (int u = 0; u < kGkOpenU; ++u) {
+            const uint32_t t = T + kGkOpenLanes * u + sl;
+            r[u] = 0;
+            cov[u] = 0;
+            if (t >= nwin) continue;
+            const uint64_t a = 16ull * t, stop = min(a + 16u, end);
+            uint64_t pos = max(a, (uint64_t)vb);
+            uint32_t q = 0;   // the last piece that starts at or before pos
+#pragma unroll
+            for (uint32_t step = HYOBFS_GECKO_MAX_CHUNKS / 2; step; step >>= 1)
+                q = M.pre[q + step] <= (uint32_t)(pos - vb) ? q + step : q;
+            while (pos < stop) {
+                const uint32_t p = (uint32_t)(pos - vb);
+                while (M.pre[q + 1] <= p) ++q;   // also steps over empty pieces
+                const uint32_t rs = M.pre[q], RL = M.pre[q + 1] - rs;
+                const uint64_t se = min((uint64_t)vb + rs + RL, stop);
+                const int64_t base = (int64_t)a - (int64_t)vb - (int64_t)rs;   // piece byte of window byte 0: -15 .. RL - 1
+                const uint8_t* s = wire + M.src[q];
+                const gk_u128 key = M.key[2 * q + (t & 1u)];
+                if (pos == a && se == a + 16u) {
+                    r[u] = gk_load16u(s + base) ^ key;
+                    cov[u] = 0xFFFFu;
+                    break;
+                }
+                // a piece edge: the load is clamped to the piece, taken from the 32 bytes around the window
+                const int64_t room = RL >= 16 ? (int64_t)RL - 16 : 0;
+                const uint32_t adv = base > 0 ? (uint32_t)(base < room ? base : room) : 0u;
+                const gk_u128 X = region_bytes(s + adv, min(RL - adv, 32u), (int)(base - adv), (uint32_t)(pos - a),
+                                               (uint32_t)(se - a));
+                r[u] |= (X ^ key) & gk_mask((uint32_t)(pos - a), (uint32_t)(se - a));
+                cov[u] |= ((1u << (uint32_t)(se - pos)) - 1u) << (uint32_t)(pos - a);
+                pos = se;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kGkOpenU; ++u) store_window(wbase + 16ull * (T + kGkOpenLanes * u + sl), r[u], cov[u]);
+    }
+}
+
+__global__ __launch_bounds__(64 * kGkOpenWaves) void gecko_open_kernel(GeckoOpenArgs A) {
+    __shared__ GkOpenMsg s_msg[kGkOpenWaves][kGkOpenPerWave];
+    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const uint32_t sub = lane / kGkOpenLanes, sl = lane % kGkOpenLanes;
+    const uint64_t j0 = ((uint64_t)blockIdx.x * kGkOpenWaves + wid) * kGkOpenPerWave;
+    if (j0 >= A.m) return;   // whole waves
+    const uint64_t j = j0 + sub;
+    const bool live = j < A.m;
+    uint64_t b = 0, e = 0;
+    if (live) {
+        b = A.msg_first[j];
+        e = A.msg_first[j + 1];
+    }
+    const bool list_ok = e > b && e - b <= HYOBFS_GECKO_MAX_CHUNKS;
+    const uint32_t cnt = list_ok ? (uint32_t)(e - b) : 0u;
+    // ---- lane sl: slot sl of the list
+    uint32_t len = 0, po = 0, bad = 0, slot = 0;
+    uint64_t src = 0;
+    if (sl < cnt) {
+        slot = A.chunk_idx[b + sl];
+        if (slot >= A.n) {
+            bad = 1;
+        } else {
+            const hyobfs_gecko_parsed r = A.parsed[slot];
+            const uint32_t wl = A.wire_len[slot];
+            const bool kind = r.status == HYOBFS_GECKO_FRAGMENT || (r.status == HYOBFS_GECKO_PASS && cnt == 1);
+            // the payload ends where the datagram does: what keeps every load inside it
+            if (!kind || wl < HYOBFS_SALT_LEN || (uint64_t)r.payload_off + r.payload_len != (uint64_t)wl - HYOBFS_SALT_LEN) {
+                bad = 1;
+            } else {
+                len = r.payload_len;
+                po = r.payload_off;
+                src = A.wire_off[slot] + HYOBFS_SALT_LEN + po;
+            }
+        }
+    }
+    uint64_t inc = len;   // inclusive scan and "any" over the message's 16 lanes
+#pragma unroll
+    for (uint32_t d = 1; d < kGkOpenLanes; d <<= 1) {
+        const uint64_t y = __shfl_up(inc, d, 64);
+        const uint32_t z = __shfl_xor(bad, (int)d, 64);
+        if (sl >= d) inc += y;
+        bad |= z;
+    }
+    const uint64_t total = __shfl(inc, (int)(lane | (kGkOpenLanes - 1)), 64);
+    int32_t st = HYOBFS_OK;
+    if (live) {
+        st = (!list_ok || bad) ? HYOBFS_GECKO_ERR_PLAN : total > A.out_cap[j] ? HYOBFS_GECKO_ERR_CAP : HYOBFS_OK;
+        if (sl == 0) {
+            A.status[j] = st;
+            A.out_len[j] = st == HYOBFS_OK ? (uint32_t)total : 0u;
+        }
+    }
+    const bool go = live && st == HYOBFS_OK && total != 0;   // total <= out_cap[j] < 2^32
+    const uint64_t o = go ? A.out_off[j] : 0;
+    GkOpenMsg& M = s_msg[wid][sub];
+    if (sl <= HYOBFS_GECKO_MAX_CHUNKS) M.pre[sl] = sl <= cnt ? (uint32_t)(inc - len) : kGkNoPiece;   // [cnt] = the total
+    if (go && sl < cnt) {
+        M.src[sl] = src;
+        const uint8_t* kp = A.keys + 32ull * slot;
+        const gk_u128 k0 = gk_load16u(kp), k1 = gk_load16u(kp + 16);
+        const uint64_t kw[4] = {(uint64_t)k0, (uint64_t)(k0 >> 64), (uint64_t)k1, (uint64_t)(k1 >> 64)};
+        uint64_t kr[4];
+        const uint32_t vb = (uint32_t)((reinterpret_cast<uintptr_t>(A.out) + o) & 15u);
+        rotl_key_bytes(kw, (vb + (uint32_t)(inc - len) - po) & 31u, kr);
+        M.key[2 * sl] = (gk_u128)kr[1] << 64 | kr[0];
+        M.key[2 * sl + 1] = (gk_u128)kr[3] << 64 | kr[2];
+    }
+    hy_wave_sync();
+    if (go) gk_open_sweep(A.wire, A.out, o, (uint32_t)total, M, sl);
 }
 
 hipError_t launch_gecko_encode(const KeyParams& k, const hyobfs_gecko_batch& b, hipStream_t s) {
@@ -622,6 +806,32 @@ hipError_t launch_gecko_parse(const uint8_t* in, const uint64_t* in_off, const u
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(gecko_parse_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, s, in, in_off, in_len,
                        n, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_gecko_peek(const KeyParams& k, const uint8_t* wire, const uint64_t* wire_off, const uint32_t* wire_len,
+                             uint64_t n, hyobfs_gecko_parsed* parsed, uint8_t* keys, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint64_t blocks = (n + 255) / 256;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)blocks), block(256);
+    switch (k.salt_pos >> 3) {   // one instantiation per salt word, as launch_gecko_encode
+#define HY_CASE(w) \
+    case w: hipLaunchKernelGGL(gecko_peek_kernel<w>, grid, block, 0, s, k, wire, wire_off, wire_len, n, parsed, keys); break;
+        HY_CASE(0) HY_CASE(1) HY_CASE(2) HY_CASE(3) HY_CASE(4) HY_CASE(5) HY_CASE(6) HY_CASE(7)
+        HY_CASE(8) HY_CASE(9) HY_CASE(10) HY_CASE(11) HY_CASE(12) HY_CASE(13) HY_CASE(14) HY_CASE(15)
+#undef HY_CASE
+        default: return hipErrorInvalidValue;   // salt_pos is below 128 by construction
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_gecko_open(const GeckoOpenArgs& a, hipStream_t s) {
+    if (a.m == 0) return hipSuccess;
+    constexpr uint64_t per_block = kGkOpenWaves * kGkOpenPerWave;
+    const uint64_t blocks = (a.m + per_block - 1) / per_block;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gecko_open_kernel, dim3((uint32_t)blocks), dim3(64 * kGkOpenWaves), 0, s, a);
     return hipGetLastError();
 }
 

@@ -818,6 +818,31 @@ int hyobfs_gecko_parse_batch(const uint8_t* in, const uint64_t* in_off, const ui
     return hyobfs::hy_status(hyobfs::launch_gecko_parse(in, in_off, in_len, n, out, static_cast<hipStream_t>(stream)));
 }
 
+int hyobfs_gecko_peek_batch(hyobfs_salamander* c, const uint8_t* wire, const uint64_t* wire_off, const uint32_t* wire_len,
+                            uint64_t n, hyobfs_gecko_parsed* parsed, uint8_t* keys, void* stream) {
+    if (n == 0) return HYOBFS_OK;
+    if (!c || !wire || !wire_off || !wire_len || !parsed || !keys) return HYOBFS_ERR_INVALID;
+    DeviceGuard g(c->device);
+    if (!g.ok) return HYOBFS_ERR_HIP;
+    const hipError_t e =
+        hyobfs::launch_gecko_peek(c->kp, wire, wire_off, wire_len, n, parsed, keys, static_cast<hipStream_t>(stream));
+    return e == hipErrorInvalidValue ? HYOBFS_ERR_INVALID : hyobfs::hy_status(e);
+}
+
+int hyobfs_gecko_open_batch(const uint8_t* wire, const uint64_t* wire_off, const uint32_t* wire_len,
+                            const hyobfs_gecko_parsed* parsed, const uint8_t* keys, uint64_t n, const uint32_t* chunk_idx,
+                            const uint64_t* msg_first, uint64_t m, uint8_t* out, const uint64_t* out_off,
+                            const uint32_t* out_cap, uint32_t* out_len, int32_t* status, void* stream) {
+    if (m == 0) return HYOBFS_OK;
+    if (!wire || !wire_off || !wire_len || !parsed || !keys || !chunk_idx || !msg_first || !out || !out_off || !out_cap ||
+        !out_len || !status)
+        return HYOBFS_ERR_INVALID;
+    const hyobfs::GeckoOpenArgs a{wire, wire_off, wire_len, parsed, keys, n, chunk_idx, msg_first, m, out, out_off, out_cap,
+                                  out_len, status};
+    const hipError_t e = hyobfs::launch_gecko_open(a, static_cast<hipStream_t>(stream));
+    return e == hipErrorInvalidValue ? HYOBFS_ERR_INVALID : hyobfs::hy_status(e);
+}
+
 int hyobfs_salamander_obfuscate_host(hyobfs_salamander* c, const hyobfs_batch* b, uint64_t chunk) {
     return run_host(c, b, chunk, true);
 }

@@ -99,6 +99,27 @@ hipError_t launch_keys(const KeyParams& k, const uint64_t* salts, uint8_t* keys,
 hipError_t launch_gecko_encode(const KeyParams& k, const hyobfs_gecko_batch& b, hipStream_t s);
 hipError_t launch_gecko_parse(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint64_t n,
                               hyobfs_gecko_parsed* out, hipStream_t s);
+// hyobfs_gecko_peek_batch / hyobfs_gecko_open_batch (include/hyobfs_gecko.h); hipErrorInvalidValue: a batch
+// too large for one grid
+hipError_t launch_gecko_peek(const KeyParams& k, const uint8_t* wire, const uint64_t* wire_off, const uint32_t* wire_len,
+                             uint64_t n, hyobfs_gecko_parsed* parsed, uint8_t* keys, hipStream_t s);
+struct GeckoOpenArgs {
+    const uint8_t* wire;
+    const uint64_t* wire_off;
+    const uint32_t* wire_len;
+    const hyobfs_gecko_parsed* parsed;
+    const uint8_t* keys;
+    uint64_t n;
+    const uint32_t* chunk_idx;
+    const uint64_t* msg_first;
+    uint64_t m;
+    uint8_t* out;
+    const uint64_t* out_off;
+    const uint32_t* out_cap;
+    uint32_t* out_len;
+    int32_t* status;
+};
+hipError_t launch_gecko_open(const GeckoOpenArgs& a, hipStream_t s);
 hipError_t launch_synth_stream(uint8_t* dst, uint64_t nbytes, uint64_t seed, uint64_t start,
                                hipStream_t s);
 hipError_t launch_synth_u64(uint64_t* dst, uint64_t n, uint64_t seed, uint64_t first,

@@ -198,54 +198,7 @@ __global__ __launch_bounds__(kTileMsgs) void udp_index_kernel(FragArgs A) {
 }
 
 // ---------------------------------------------------------------- windows
-// `X` holds the 16 bytes whose first is region byte `lw`; the result holds, at byte
-// j, region byte base + j (|base - lw| < 16)
-__device__ __forceinline__ u128 shift_into_place(u128 V, int base, int lw) {
-    const int d = base - lw;
-    return d >= 0 ? (V >> (8 * d)) : (V << (8 * -d));
-}
-
-// The bytes [sb, se) of a window (relative to the window) out of a region of RL
-// bytes at src, where window byte 0 is region byte `base` (negative: the region
-// starts inside the window).  One 16-byte load inside the region, shifted into
-// place; a region shorter than that comes from two overlapping shorter loads.
-__device__ __forceinline__ u128 region_bytes(const uint8_t* __restrict__ src, uint32_t RL, int base, uint32_t sb,
-                                             uint32_t se) {
-    if (RL >= 16) {
-        const int lw = min(max(base, 0), (int)RL - 16);
-        return shift_into_place(load16u(src + lw), base, lw);
-    }
-    // fewer than 16 bytes: the whole region from two overlapping loads of 8, 4 or 2 bytes (or its one
-    // byte), every one inside it, then shifted like a 16-byte load at region byte 0
-    (void)sb;
-    (void)se;
-    uint64_t lo, hi;
-    uint32_t w;
-    if (RL >= 8) {
-        w = 8;
-        lo = load8u(src);
-        hi = load8u(src + RL - 8);
-    } else if (RL >= 4) {
-        uint32_t a, b;
-        w = 4;
-        __builtin_memcpy(&a, src, 4);
-        __builtin_memcpy(&b, src + RL - 4, 4);
-        lo = a;
-        hi = b;
-    } else if (RL >= 2) {
-        uint16_t a, b;
-        w = 2;
-        __builtin_memcpy(&a, src, 2);
-        __builtin_memcpy(&b, src + RL - 2, 2);
-        lo = a;
-        hi = b;
-    } else {
-        w = 1;
-        lo = hi = src[0];
-    }
-    const u128 V = (u128)lo | ((u128)hi << (8 * (RL - w)));   // the bytes both loads hold are equal
-    return shift_into_place(V, base, 0);
-}
+// (shift_into_place, region_bytes and store_window: salamander_device.h)
 
 // p / d for p < 2^21 (a message's output: at most 255 headers of at most 4096 bytes, and its data) and
 // d >= 9: the float quotient is off by at most one, which the two compares put right
@@ -265,13 +218,6 @@ __device__ __forceinline__ u128 fixed_header(uint32_t session, uint32_t pid, uin
     uint64_t hi = 0;
     for (uint32_t j = 0; j < vl; ++j) hi |= (uint64_t)varint_byte(addr_len, vl, j) << (8 * j);
     return (u128)hi << 64 | lo;
-}
-
-__device__ __forceinline__ void store_window(uint8_t* dst, u128 r, uint32_t cov) {   // dst 16-aligned
-    if (cov == 0xFFFFu)
-        store16_stream(dst, r);
-    else if (cov)
-        store_masked(dst, r, cov);
 }
 
 // ---------------------------------------------------------------- the write kernel

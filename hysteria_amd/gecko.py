@@ -19,10 +19,13 @@ reference (Go)                                 here
 ``randomPadLen`` / ``randIntn`` (:131-153)     ``random_pad_len`` / ``rand_intn``
 (new) one device pass over many frames         ``plan_fragments`` + ``encode_batch`` (GPU)
 (new) device parse of received datagrams       ``parse_batch`` (GPU)
+(new) the receive side without the padding     ``peek_batch`` (GPU), ``Reassembler`` (the C
+                                               state machine over indices), ``open_batch``
+                                               (GPU); ``GeckoReceiver`` runs the three
 =============================================  ==============================================
 
 The frame codec and the device batch calls go through ``include/hyobfs_gecko.h``
-(``libhyobfs.so``); reassembly state stays on the host, as in the reference.
+(``libhyobfs.so``); the reassembly table stays on the host, as in the reference.
 """
 from __future__ import annotations
 
@@ -35,7 +38,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._dev import _ptr, _stream
+from ._dev import _ptr, _stream, _to
 from ._lib import _i32, _i64, _sz, _u32, _u64, _vp, check
 
 FLAG_FRAGMENT = 0x80
@@ -53,6 +56,9 @@ SALT_LEN = 8
 ERR_TRUNCATED = -20
 ERR_INVALID = -21
 PASS, FRAGMENT, EMPTY = 0, 1, -22
+ERR_CAP, ERR_PLAN = -23, -24                          # open_batch, per message
+RX_PENDING, RX_PASS, RX_COMPLETE, RX_DROPPED = 0, 1, 2, 3   # Reassembler.feed
+REASSEMBLY_TTL_MS = 8000
 
 
 class FrameTruncatedError(ValueError):
@@ -101,6 +107,15 @@ _SIG = {   # include/hyobfs_gecko.h
     "hyobfs_gecko_encode_batch": (_i32, [_vp, ctypes.POINTER(HyobfsGeckoBatch), _vp]),
     "hyobfs_gecko_parse_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "hyobfs_gecko_random_pad_key": (_i32, [_vp, _vp]),
+    "hyobfs_gecko_peek_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "hyobfs_gecko_open_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hyobfs_gecko_reassembler_new": (_vp, []),
+    "hyobfs_gecko_reassembler_free": (None, [_vp]),
+    "hyobfs_gecko_reassembler_feed": (_i32, [_vp, _vp, _u32, _vp, _u64, _u64, _vp, ctypes.POINTER(_u32),
+                                             ctypes.POINTER(_u32)]),
+    "hyobfs_gecko_reassembler_gc": (None, [_vp, _u64]),
+    "hyobfs_gecko_reassembler_pending": (_u64, [_vp]),
+    "hyobfs_gecko_reassembler_released": (_u64, [_vp, _vp, _u64]),
 }
 
 
@@ -417,3 +432,191 @@ def parse_batch(inp, in_off, in_len, n: int, out, stream=None) -> None:
     (PARSED_DTYPE records, 16 bytes each)."""
     check(_glib().hyobfs_gecko_parse_batch(_ptr(inp), _ptr(in_off), _ptr(in_len), n, _ptr(out),
                                            _stream(stream, out)), "gecko_parse_batch")
+
+
+# ------------------------------------------------- receive side without the padding
+def peek_batch(obfuscator, wire, wire_off, wire_len, n: int, parsed, keys, stream=None) -> None:
+    """hyobfs_gecko_peek_batch: for n still obfuscated device datagrams, the Salamander
+    key (32 bytes each into ``keys``) and the PARSED_DTYPE record of the plaintext, read
+    from the salt and at most five bytes behind it."""
+    lib = _glib(getattr(obfuscator, "_lib", None))
+    check(lib.hyobfs_gecko_peek_batch(obfuscator._h, _ptr(wire), _ptr(wire_off), _ptr(wire_len), n, _ptr(parsed),
+                                      _ptr(keys), _stream(stream, parsed)), "gecko_peek_batch")
+
+
+def open_batch(wire, wire_off, wire_len, parsed, keys, n: int, chunk_idx, msg_first, m: int, out, out_off, out_cap,
+               out_len, status, stream=None) -> None:
+    """hyobfs_gecko_open_batch: m messages, each the deobfuscated payloads of the slots
+    its list names (a table of n slots as peek_batch left them), concatenated."""
+    check(_glib().hyobfs_gecko_open_batch(_ptr(wire), _ptr(wire_off), _ptr(wire_len), _ptr(parsed), _ptr(keys), n,
+                                          _ptr(chunk_idx), _ptr(msg_first), m, _ptr(out), _ptr(out_off), _ptr(out_cap),
+                                          _ptr(out_len), _ptr(status), _stream(stream, status)), "gecko_open_batch")
+
+
+class Reassembler:
+    """hyobfs_gecko_reassembler: acceptChunk, gcExpired and evictOldestLocked
+    (gecko.go:199-304) over parsed records and the caller's tags, on the caller's
+    millisecond clock.  It never sees a payload."""
+
+    def __init__(self):
+        self._h = _glib().hyobfs_gecko_reassembler_new()
+        if not self._h:
+            raise MemoryError("hyobfs_gecko_reassembler_new")
+        self._tags = (ctypes.c_uint64 * MAX_FRAGMENT_CHUNKS)()
+
+    def feed(self, source: bytes, rec, tag: int, now_ms: int) -> tuple[int, list[int], int]:
+        """(RX_PENDING | RX_PASS | RX_COMPLETE | RX_DROPPED, tags, msg_len): ``rec`` is a
+        PARSED_DTYPE record (or its 16 bytes); ``tags`` is in chunk order, empty unless
+        RX_PASS / RX_COMPLETE."""
+        raw = rec if isinstance(rec, (bytes, bytearray)) else np.asarray(rec).tobytes()
+        n, ln = ctypes.c_uint32(), ctypes.c_uint32()
+        st = _glib().hyobfs_gecko_reassembler_feed(self._h, source, len(source), raw, tag, now_ms,
+                                                   ctypes.addressof(self._tags), ctypes.byref(n), ctypes.byref(ln))
+        if st < 0:
+            raise _lib.HyobfsError(st, "gecko_reassembler_feed")
+        return st, list(self._tags[:n.value]), ln.value
+
+    def gc(self, now_ms: int) -> None:
+        _glib().hyobfs_gecko_reassembler_gc(self._h, now_ms)
+
+    def pending(self) -> int:
+        return int(_glib().hyobfs_gecko_reassembler_pending(self._h))
+
+    def released(self) -> list[int]:
+        """The tags of chunks dropped by gc or eviction since the last call, oldest first."""
+        lib = _glib()
+        k = int(lib.hyobfs_gecko_reassembler_released(self._h, None, 0))
+        if k == 0:
+            return []
+        buf = (ctypes.c_uint64 * k)()
+        return list(buf[:lib.hyobfs_gecko_reassembler_released(self._h, ctypes.addressof(buf), k)])
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _glib().hyobfs_gecko_reassembler_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter shutdown
+            pass
+
+
+class GeckoReceiver:
+    """The receive pipeline on the obfuscator's device: wire datagrams in, what a
+    sequence of ReadFrom calls (gecko.go:169-197) returns out.
+
+    Received datagrams stay on the device, still obfuscated, in a table of
+    ``BUFFER_SIZE``-byte slots until their message is complete; only the 16-byte
+    records cross to the host, and only payload bytes are ever deobfuscated.  The
+    table has ``MAX_REASSEMBLY * (MAX_FRAGMENT_CHUNKS - 1) + max_batch`` slots: every
+    pending entry lacks at least one chunk, so it cannot run out."""
+
+    def __init__(self, obfuscator, max_batch: int = 64):
+        import torch
+        self._o, self.max_batch = obfuscator, max_batch
+        self._dev = dev = torch.device("cuda", obfuscator.device)
+        self.slots = S = MAX_REASSEMBLY * (MAX_FRAGMENT_CHUNKS - 1) + max_batch
+        self._wire = torch.zeros((S, BUFFER_SIZE), dtype=torch.uint8, device=dev)
+        self._off = torch.arange(S, dtype=torch.int64, device=dev) * BUFFER_SIZE
+        self._len = torch.zeros(S, dtype=torch.int32, device=dev)
+        self._parsed = torch.zeros((S, PARSED_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+        self._keys = torch.zeros((S, 32), dtype=torch.uint8, device=dev)
+        self._free = list(range(S - 1, -1, -1))   # a stack: slot 0 first
+        self._pinned: set[int] = set()            # slots of chunks that wait for the rest of their message
+        self._r = Reassembler()
+
+    @property
+    def free_slots(self) -> int:
+        return len(self._free)
+
+    @property
+    def pinned_slots(self) -> int:
+        return len(self._pinned)
+
+    def pending(self) -> int:
+        return self._r.pending()
+
+    def gc(self, now_ms: int) -> None:
+        """gcExpired; the slots of the dropped chunks are free again."""
+        self._r.gc(now_ms)
+        self._release()
+
+    def _release(self) -> None:
+        for t in self._r.released():
+            self._pinned.discard(t)
+            self._free.append(t)
+
+    def push(self, datagrams, addrs, now_ms: int):
+        """Wire datagrams (bytes, as read from the socket) and their source addresses,
+        in arrival order; returns [(payload, addr), ...] in the order of the datagrams
+        that produced them, each with the address of the datagram that completed it.
+        A datagram longer than BUFFER_SIZE is cut there, as the read buffer cuts it."""
+        out = []
+        for at in range(0, len(datagrams), self.max_batch):
+            out += self._push(datagrams[at:at + self.max_batch], addrs[at:at + self.max_batch], now_ms)
+        return out
+
+    def _push(self, datagrams, addrs, now_ms):
+        import torch
+        n, dev = len(datagrams), self._dev
+        if n == 0:
+            return []
+        slots = [self._free.pop() for _ in range(n)]
+        fed, done = 0, []   # datagrams handed to the reassembler; slots to free when this push is over
+        try:
+            datagrams = [bytes(d)[:BUFFER_SIZE] for d in datagrams]
+            lens = np.array([len(d) for d in datagrams], np.int32)
+            width = max(16, -(-int(lens.max()) // 16) * 16)   # the rows go up as wide as the longest datagram
+            rows = np.zeros((n, width), np.uint8)
+            for i, d in enumerate(datagrams):
+                rows[i, :len(d)] = np.frombuffer(d, np.uint8)
+            idx = torch.from_numpy(np.array(slots, np.int64)).to(dev)
+            d_lens = torch.from_numpy(lens).to(dev)
+            self._wire[:, :width].index_copy_(0, idx, torch.from_numpy(rows).to(dev))   # straight into their slots
+            self._len.index_copy_(0, idx, d_lens)
+            # peek over the slots; it numbers its outputs by datagram, the table by slot
+            d_parsed = torch.empty((n, PARSED_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            d_keys = torch.zeros((n, 32), dtype=torch.uint8, device=dev)
+            peek_batch(self._o, self._wire, self._off[idx], d_lens, n, d_parsed, d_keys)
+            self._parsed.index_copy_(0, idx, d_parsed)
+            self._keys.index_copy_(0, idx, d_keys)
+            recs = np.frombuffer(d_parsed.cpu().numpy().tobytes(), PARSED_DTYPE)
+            lists, caps, who = [], [], []
+            for i, slot in enumerate(slots):
+                st, tags, msg_len = self._r.feed(str(addrs[i]).encode(), recs[i], slot, now_ms)
+                fed = i + 1
+                if st == RX_PENDING:
+                    self._pinned.add(slot)
+                elif st == RX_DROPPED:
+                    done.append(slot)
+                else:   # RX_PASS, RX_COMPLETE
+                    lists.append(tags)
+                    caps.append(msg_len)
+                    who.append(addrs[i])
+                    self._pinned.difference_update(tags)
+                    done += tags
+            if not lists:
+                return []
+            m = len(lists)
+            msg_first = np.zeros(m + 1, np.uint64)
+            np.cumsum([len(l) for l in lists], out=msg_first[1:])
+            out_off = np.zeros(m, np.uint64)
+            np.cumsum(np.array(caps[:-1], np.uint64), out=out_off[1:])
+            d_out = torch.empty(int(sum(caps)) + 16, dtype=torch.uint8, device=dev)
+            d_olen = torch.empty(m, dtype=torch.int32, device=dev)
+            d_st = torch.empty(m, dtype=torch.int32, device=dev)
+            open_batch(self._wire, self._off, self._len, self._parsed, self._keys, self.slots,
+                       _to(dev, np.array([t for l in lists for t in l], np.uint32)), _to(dev, msg_first), m, d_out,
+                       _to(dev, out_off), _to(dev, np.array(caps, np.uint32)), d_olen, d_st)
+            h_st, h_out = d_st.cpu().numpy(), d_out.cpu().numpy()
+            if h_st.any():   # cannot happen: the lists come from the reassembler, the caps from its sums
+                raise _lib.HyobfsError(int(h_st[h_st != 0][0]), "gecko_open_batch")
+            return [(h_out[int(o):int(o) + c].tobytes(), a) for o, c, a in zip(out_off, caps, who)]
+        finally:   # also when a call raised: no slot is lost
+            self._release()   # evictions of this push
+            self._free += done + slots[fed:]
+
+    def close(self) -> None:
+        self._r.close()

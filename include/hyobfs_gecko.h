@@ -6,12 +6,28 @@
  * own Salamander datagram
  *     salt(8) || ( 0x80 | msgID | chunkIdx<<4|total | padLen(BE16) | pad | chunk ) ^ key
  * and padded so the datagram lands in [min_pkt, max_pkt]; short-header packets
- * pass through as plain Salamander datagrams.  The per-byte work -- header,
- * padding, chunk copy and the Salamander XOR -- runs on the GPU in one pass
- * over a batch of frames (hyobfs_gecko_encode_batch); the receive side parses
- * deobfuscated datagrams on the GPU (hyobfs_gecko_parse_batch).  The random
- * choices (chunk counts, pad lengths, msgIDs) and reassembly stay on the host,
- * as in the reference (gecko.go:199-304).
+ * pass through as plain Salamander datagrams.  The per-byte work runs on the
+ * GPU in both directions; the random choices (chunk counts, pad lengths,
+ * msgIDs) and the reassembly table stay on the host, as in the reference.
+ *
+ *   reference (Go)                                   here
+ *   ------------------------------------------------ ------------------------------------------------
+ *   encodeFrame (gecko_frame.go:39-61)               hyobfs_gecko_encode_frame
+ *   decodeFrame (gecko_frame.go:65-86)               hyobfs_gecko_decode_frame
+ *   randomPadLen (gecko.go:131-138)                  hyobfs_gecko_pad_len
+ *   writeFragmented + Obfuscate (gecko.go:112-129)   hyobfs_gecko_encode_batch (device: header, padding,
+ *                                                    chunk and the XOR in one pass)
+ *   ReadFrom's classification (gecko.go:178-190)     hyobfs_gecko_parse_batch (device, deobfuscated input)
+ *   Deobfuscate's key + that classification          hyobfs_gecko_peek_batch (device, wire input: reads the
+ *   (salamander.go:74-91, gecko.go:178-190)          salt and at most five bytes of each datagram)
+ *   acceptChunk (gecko.go:199-249), the map and      hyobfs_gecko_reassembler_feed (host, over the caller's
+ *   its two caps                                     tags: no payload byte is touched)
+ *   gcExpired (gecko.go:266-274)                     hyobfs_gecko_reassembler_gc
+ *   evictOldestLocked (gecko.go:290-304)             inside _feed (rule 2 there; the tie rule is stated)
+ *   len(g.reassembly)                                hyobfs_gecko_reassembler_pending
+ *   (the chunk copies the garbage collector frees)   hyobfs_gecko_reassembler_released
+ *   acceptChunk's copies + Deobfuscate's XOR         hyobfs_gecko_open_batch (device: only payload bytes
+ *   (gecko.go:230-246, salamander.go:82-84)          are read, XORed and written, once)
  *
  * Plain C ABI: pointers, sizes, integer status codes.
  */
@@ -46,6 +62,14 @@ extern "C" {
 #define HYOBFS_GECKO_PASS 0        /* top bit clear: short header or garbage, passed through (gecko.go:183-185) */
 #define HYOBFS_GECKO_FRAGMENT 1    /* a valid fragment frame */
 #define HYOBFS_GECKO_EMPTY (-22)   /* zero-length datagram: skipped by ReadFrom (gecko.go:178-180) */
+/* per-message results of hyobfs_gecko_open_batch (status[j]) */
+#define HYOBFS_GECKO_ERR_CAP (-23)   /* the message is longer than out_cap[j] */
+#define HYOBFS_GECKO_ERR_PLAN (-24)  /* a chunk list that cannot be opened */
+/* results of hyobfs_gecko_reassembler_feed */
+#define HYOBFS_GECKO_RX_PENDING 0    /* stored; the message is not complete yet */
+#define HYOBFS_GECKO_RX_PASS 1       /* not a fragment: the datagram is the message */
+#define HYOBFS_GECKO_RX_COMPLETE 2   /* the last missing chunk: tags_out lists the message */
+#define HYOBFS_GECKO_RX_DROPPED 3    /* dropped silently, as the reference does */
 
 /* frameHeader (gecko_frame.go:30-35) */
 typedef struct hyobfs_gecko_header {
@@ -153,6 +177,121 @@ typedef struct hyobfs_gecko_parsed {
  */
 int hyobfs_gecko_parse_batch(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint64_t n,
                              hyobfs_gecko_parsed* out, void* stream);
+
+/*
+ * The receive side without the padding.  Three steps:
+ *
+ *   hyobfs_gecko_peek_batch       device: key and 16-byte record of every wire datagram
+ *   hyobfs_gecko_reassembler_*    host: which datagrams form which message (indices only)
+ *   hyobfs_gecko_open_batch       device: the payloads of every ready message, deobfuscated
+ *                                 and concatenated
+ *
+ * A fragment datagram in the default [512, 1200] band is mostly padding, which the
+ * receiver never needs: peek reads 13 bytes of it, open reads its payload only.
+ *
+ * peek, for each still obfuscated wire datagram wire[wire_off[i], +wire_len[i])
+ * (device pointers):
+ *   wire_len[i] <= 8   parsed[i] = {HYOBFS_GECKO_EMPTY, 0...}; keys[32 i, +32) is not
+ *                      written (Deobfuscate returns 0, salamander.go:75-77; ReadFrom
+ *                      skips it, gecko.go:178-180)
+ *   otherwise          keys[32 i, +32) = BLAKE2b-256(PSK || wire[0, 8)); parsed[i] is the
+ *                      record hyobfs_gecko_parse_batch writes for the deobfuscated
+ *                      datagram of wire_len[i] - 8 bytes: the same checks in the same
+ *                      order, payload_off / payload_len relative to that plaintext
+ * It reads the salt and at most the five bytes behind it, and never a byte at or past
+ * wire_off[i] + wire_len[i]; it writes parsed[0, n) and the stated key ranges only.
+ * One lane per datagram; asynchronous on `stream`.  n == 0 returns HYOBFS_OK before
+ * any pointer is looked at; a null pointer returns HYOBFS_ERR_INVALID.
+ */
+int hyobfs_gecko_peek_batch(hyobfs_salamander* ctx, const uint8_t* wire, const uint64_t* wire_off,
+                            const uint32_t* wire_len, uint64_t n, hyobfs_gecko_parsed* parsed, uint8_t* keys,
+                            void* stream);
+
+/*
+ * acceptChunk (gecko.go:199-249) and its maintenance (gecko.go:266-304) as a state
+ * machine over the caller's 64-bit tags (a datagram's slot, say); it never sees a
+ * payload byte.  `source` is opaque bytes of any length and stands for the
+ * reference's addr.String(); time is the caller's millisecond clock, passed in.
+ * One mutex: calls on one reassembler may come from several threads.
+ *
+ * feed, by rec->status:
+ *   PASS       HYOBFS_GECKO_RX_PASS, tags_out[0] = tag, *n_out = 1, *msg_len =
+ *              payload_len; the state is untouched (gecko.go:183-185)
+ *   EMPTY,     HYOBFS_GECKO_RX_DROPPED, *n_out = 0 ("malformed frame; drop silently",
+ *   ERR_*      gecko.go:187-190); so is a FRAGMENT record decodeFrame could not have
+ *              produced (total outside [2, 8] or index >= total), before any state
+ *   FRAGMENT   acceptChunk's rules in its order, key = (source, msg_id):
+ *     1. a new key while its source has HYOBFS_GECKO_MAX_PER_SOURCE entries: DROPPED
+ *     2. a new key while HYOBFS_GECKO_MAX_REASSEMBLY entries exist: the entry with the
+ *        earliest deadline is evicted first
+ *     3. the new entry's deadline is now_ms + HYOBFS_GECKO_REASSEMBLY_TTL_MS, set at
+ *        creation and never refreshed
+ *     4. an existing entry with another total: DROPPED
+ *     5. a filled index: DROPPED (the first copy wins)
+ *     6. otherwise the chunk's tag and payload_len are stored
+ *     7. the last chunk: HYOBFS_GECKO_RX_COMPLETE, tags_out[0, total) the tags in chunk
+ *        order, *n_out = total, *msg_len = the sum of the payload lengths (saturating at
+ *        UINT32_MAX); the entry is deleted and its source's count decremented, so a
+ *        later chunk with the same msg_id starts a new entry
+ *     8. otherwise HYOBFS_GECKO_RX_PENDING, *n_out = 0
+ * HYOBFS_ERR_INVALID for a null argument (source may be null when source_len is 0);
+ * HYOBFS_ERR_NOMEM when the table cannot grow (the chunk is not stored, the table stays as it was,
+ * but for an eviction already made).
+ *
+ * Stated divergence: evictOldestLocked walks a Go map, so which of several entries
+ * with the same earliest deadline it drops is unspecified in the reference.  Here the
+ * one created first goes.  gc likewise drops in (deadline, creation) order, which only
+ * shows in the order of `released`.
+ */
+typedef struct hyobfs_gecko_reassembler hyobfs_gecko_reassembler;
+hyobfs_gecko_reassembler* hyobfs_gecko_reassembler_new(void);
+void hyobfs_gecko_reassembler_free(hyobfs_gecko_reassembler* r);
+int hyobfs_gecko_reassembler_feed(hyobfs_gecko_reassembler* r, const uint8_t* source, uint32_t source_len,
+                                  const hyobfs_gecko_parsed* rec, uint64_t tag, uint64_t now_ms, uint64_t tags_out[8],
+                                  uint32_t* n_out, uint32_t* msg_len);
+/* gcExpired: drops every entry with now_ms > deadline (strict, as now.After).  Out of memory it stops
+   early; the next call goes on. */
+void hyobfs_gecko_reassembler_gc(hyobfs_gecko_reassembler* r, uint64_t now_ms);
+/* len(g.reassembly) */
+uint64_t hyobfs_gecko_reassembler_pending(const hyobfs_gecko_reassembler* r);
+/*
+ * The tags of chunks whose entries gc or an eviction dropped since they were last
+ * drained, oldest first: the caller frees what they stand for.  Copies at most `cap`
+ * of them to `tags`, forgets those and returns their number; with tags null or cap 0 it
+ * returns how many wait.  Tags handed out by a COMPLETE never appear here.
+ */
+uint64_t hyobfs_gecko_reassembler_released(hyobfs_gecko_reassembler* r, uint64_t* tags, uint64_t cap);
+
+/*
+ * Open m messages.  wire, wire_off, wire_len, parsed and keys are a table of n
+ * datagram slots as hyobfs_gecko_peek_batch left them (device pointers); the table may
+ * span many received batches, which is how chunks that arrived in different batches
+ * meet.  Message j is the concatenation, in list order, of the opened payloads of the
+ * slots chunk_idx[msg_first[j] .. msg_first[j + 1]); for slot c and payload byte t
+ *     out = wire[wire_off[c] + 8 + payload_off + t] ^ keys[32 c + (payload_off + t) % 32]
+ * (the key phase is the plaintext index, salamander.go:82-84).  A PASS record has
+ * payload_off 0 and payload_len wire_len - 8, so a list of one PASS slot yields the
+ * whole deobfuscated datagram.  out_len[j] = the sum of the payload lengths (taken in
+ * 64 bits), the bytes at out + out_off[j].  status[j]:
+ *   HYOBFS_OK
+ *   HYOBFS_GECKO_ERR_CAP    the sum exceeds out_cap[j]
+ *   HYOBFS_GECKO_ERR_PLAN   an empty list, more than HYOBFS_GECKO_MAX_CHUNKS entries, an
+ *                           index >= n, a slot whose status is neither FRAGMENT nor PASS,
+ *                           a PASS slot in a list longer than one, or a slot with
+ *                           payload_off + payload_len != wire_len - 8
+ * Both errors write nothing of the message and set out_len[j] = 0.  A list may name a
+ * slot twice; an empty payload is legal (a 1-byte message split in two has one).
+ * No byte of a datagram's salt, header or padding is read and no load leaves
+ * wire[wire_off[c], +wire_len[c]); exactly out[out_off[j], +out_len[j]), out_len[0, m)
+ * and status[0, m) are written.  Runs on the current device, asynchronous on `stream`.
+ * m == 0 returns HYOBFS_OK before any pointer is looked at; a null pointer returns
+ * HYOBFS_ERR_INVALID.
+ */
+int hyobfs_gecko_open_batch(const uint8_t* wire, const uint64_t* wire_off, const uint32_t* wire_len,
+                            const hyobfs_gecko_parsed* parsed, const uint8_t* keys, uint64_t n,
+                            const uint32_t* chunk_idx, const uint64_t* msg_first, uint64_t m, uint8_t* out,
+                            const uint64_t* out_off, const uint32_t* out_cap, uint32_t* out_len, int32_t* status,
+                            void* stream);
 
 #ifdef __cplusplus
 }
