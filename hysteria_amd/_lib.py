@@ -147,6 +147,20 @@ _UDP_SIG = {   # include/hyobfs_udpmsg.h (hysteria_amd/udpmsg.py); declared by l
     "hyobfs_udp_assemble_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
+_u16p = ctypes.POINTER(ctypes.c_uint16)
+_ADDR_SIG = {   # include/hyobfs_addr.h (hysteria_amd/addr.py); declared by load() like the ACL's
+    "hyobfs_addr_split": (_i32, [_vp, _sz, ctypes.POINTER(_u32), ctypes.POINTER(_u32), ctypes.POINTER(_u32),
+                                 ctypes.POINTER(_u32)]),
+    "hyobfs_addr_parse_port": (_i32, [_vp, _sz, _u16p]),
+    "hyobfs_addr_parse_ip": (_i32, [_vp, _sz, _vp]),
+    "hyobfs_addr_parse": (_i32, [_vp, _sz, ctypes.POINTER(_u32), ctypes.POINTER(_u32), _vp, _vp,
+                                 ctypes.POINTER(ctypes.c_uint8), _u16p]),
+    "hyobfs_addr_format": (_i32, [_vp, _u32, ctypes.c_uint16, _vp, _sz]),
+    "hyobfs_addr_parse_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hyobfs_addr_parse_udp_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hyobfs_addr_format_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+}
+
 _lib = None
 _variants = {}   # other builds loaded side by side (in-process A/B runs, scripts/ab_variants.py)
 
@@ -184,6 +198,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         declare(lib, "acl", _ACL_SIG)
     if hasattr(lib, "hyobfs_udp_parse_batch"):   # likewise udpmsg.hip / udpmsg_host.cpp (udpmsg._ulib())
         declare(lib, "udpmsg", _UDP_SIG)
+    if hasattr(lib, "hyobfs_addr_parse_batch"):   # likewise addr.hip / addr_host.cpp (addr._adlib())
+        declare(lib, "addr", _ADDR_SIG)
     have = lib.hyobfs_abi_version()
     if have != ABI_VERSION:   # struct layouts and enum values differ between versions
         raise OSError(f"{path}: ABI version {have}, these bindings need {ABI_VERSION}: rebuild the library")

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/hyobfs.h"
+#include "../../include/hyobfs_addr.h"
 #include "conn_coalesce.h"
 #include "kernels.h"
 
@@ -497,6 +498,15 @@ const char* hyobfs_status_string(int st) {
         case HYOBFS_ERR_NO_DEVICE: return "no usable gfx950 device";
         case HYOBFS_ERR_IO: return "socket I/O error";
         case HYOBFS_ERR_CLOSED: return "use of closed connection";
+        case HYOBFS_ADDR_ERR_NO_ADDR: return "the datagram has no address";
+        case HYOBFS_ADDR_ERR_MISSING_PORT: return "missing port in address";
+        case HYOBFS_ADDR_ERR_TOO_MANY_COLONS: return "too many colons in address";
+        case HYOBFS_ADDR_ERR_MISSING_BRACKET: return "missing ']' in address";
+        case HYOBFS_ADDR_ERR_UNEXPECTED_LBRACKET: return "unexpected '[' in address";
+        case HYOBFS_ADDR_ERR_UNEXPECTED_RBRACKET: return "unexpected ']' in address";
+        case HYOBFS_ADDR_ERR_PORT: return "invalid port";
+        case HYOBFS_ADDR_ERR_TOO_LONG: return "address too long";
+        case HYOBFS_ADDR_ERR_FAMILY: return "address family is neither 4 nor 16";
         default: return "unknown status";
     }
 }
