@@ -788,17 +788,11 @@ __global__ __launch_bounds__(64 * kGkOpenWaves) void gecko_open_kernel(GeckoOpen
 
 hipError_t launch_gecko_encode(const KeyParams& k, const hyobfs_gecko_batch& b, hipStream_t s) {
     if (b.n == 0) return hipSuccess;
-    // instantiated per salt word (salamander_inst.hip's rule): the PSK's message words
-    // stay scalar, only the salt's one or two words are per lane
     const dim3 grid((uint32_t)((b.n + 255) / 256)), block(256);
-    switch (k.salt_pos >> 3) {
-#define HY_CASE(n) \
-    case n: hipLaunchKernelGGL(gecko_encode_kernel<n>, grid, block, 0, s, k, b); break;
-        HY_CASE(0) HY_CASE(1) HY_CASE(2) HY_CASE(3) HY_CASE(4) HY_CASE(5) HY_CASE(6) HY_CASE(7)
-        HY_CASE(8) HY_CASE(9) HY_CASE(10) HY_CASE(11) HY_CASE(12) HY_CASE(13) HY_CASE(14) HY_CASE(15)
-#undef HY_CASE
-    }
-    return hipGetLastError();
+    return with_salt_word(k, [&](auto sw) {   // one instantiation per salt word (kernels.h)
+        hipLaunchKernelGGL(gecko_encode_kernel<decltype(sw)::value>, grid, block, 0, s, k, b);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_gecko_parse(const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint64_t n,
@@ -815,15 +809,11 @@ hipError_t launch_gecko_peek(const KeyParams& k, const uint8_t* wire, const uint
     const uint64_t blocks = (n + 255) / 256;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const dim3 grid((uint32_t)blocks), block(256);
-    switch (k.salt_pos >> 3) {   // one instantiation per salt word, as launch_gecko_encode
-#define HY_CASE(w) \
-    case w: hipLaunchKernelGGL(gecko_peek_kernel<w>, grid, block, 0, s, k, wire, wire_off, wire_len, n, parsed, keys); break;
-        HY_CASE(0) HY_CASE(1) HY_CASE(2) HY_CASE(3) HY_CASE(4) HY_CASE(5) HY_CASE(6) HY_CASE(7)
-        HY_CASE(8) HY_CASE(9) HY_CASE(10) HY_CASE(11) HY_CASE(12) HY_CASE(13) HY_CASE(14) HY_CASE(15)
-#undef HY_CASE
-        default: return hipErrorInvalidValue;   // salt_pos is below 128 by construction
-    }
-    return hipGetLastError();
+    return with_salt_word(k, [&](auto sw) {   // one instantiation per salt word, as launch_gecko_encode
+        hipLaunchKernelGGL(gecko_peek_kernel<decltype(sw)::value>, grid, block, 0, s, k, wire, wire_off, wire_len, n, parsed,
+                           keys);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_gecko_open(const GeckoOpenArgs& a, hipStream_t s) {

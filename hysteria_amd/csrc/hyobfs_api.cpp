@@ -200,6 +200,32 @@ int ensure_stage(hyobfs_salamander* c, size_t bytes) {
     return HYOBFS_OK;
 }
 
+// A hyobfs_batch as the kernels' argument under a context's kernel setting: the one place
+// that copies its fields.  The per-packet cap and the slot fold into pkt_cap; the caller's
+// workspace (if any) is the scratch.
+BatchParams batch_params(const hyobfs_batch& b, int kernel) {
+    BatchParams bp{};
+    bp.n = b.n;
+    bp.in = b.in;
+    bp.in_off = b.in_off;
+    bp.in_stride = b.in_stride;
+    bp.in_len = b.in_len;
+    bp.len_uniform = b.len_uniform;
+    uint64_t cap = b.pkt_cap;
+    if (b.out_stride && (cap == 0 || b.out_stride < cap)) cap = b.out_stride;
+    bp.pkt_cap = (uint32_t)cap;
+    bp.salts = b.salts;
+    bp.out = b.out;
+    bp.out_cap = b.out_cap;
+    bp.out_stride = b.out_stride;
+    bp.out_off = b.out_off;
+    bp.out_len = b.out_len;
+    bp.out_total = reinterpret_cast<unsigned long long*>(b.out_total);
+    bp.scratch = b.workspace;
+    bp.kernel = kernel;
+    return bp;
+}
+
 // One datagram through the batch kernel, staged in mapped pinned memory.
 // Caller holds c->mu and has checked the reference's length rules.
 size_t run_one(hyobfs_salamander* c, bool obf, const uint8_t* in, size_t in_len,
@@ -216,8 +242,7 @@ size_t run_one(hyobfs_salamander* c, bool obf, const uint8_t* in, size_t in_len,
     if (obf) std::memcpy(h_misc, salt, HYOBFS_SALT_LEN);
     uint32_t* h_len = reinterpret_cast<uint32_t*>(h_misc + 8);
     *h_len = 0xFFFFFFFFu;
-    BatchParams b{};
-    b.kernel = c->kernel.load(std::memory_order_relaxed);
+    hyobfs_batch b{};
     b.n = 1;
     b.in = c->stage_dev;
     b.len_uniform = (uint32_t)in_len;
@@ -227,7 +252,8 @@ size_t run_one(hyobfs_salamander* c, bool obf, const uint8_t* in, size_t in_len,
     b.out_stride = W;   // one slot of exactly len(out) = W bytes
     b.pkt_cap = (uint32_t)W;
     b.out_len = reinterpret_cast<uint32_t*>(c->stage_dev + 2 * c->stage_cap + 8);
-    if (hyobfs::launch_salamander(obf, b, c->kp, c->stream) != hipSuccess) return 0;
+    const BatchParams bp = batch_params(b, c->kernel.load(std::memory_order_relaxed));
+    if (hyobfs::launch_salamander(obf, hyobfs::plan_batch(obf, bp), bp, c->kp, c->stream) != hipSuccess) return 0;
     if (hipStreamSynchronize(c->stream) != hipSuccess) return 0;
     if (*h_len != W) return 0;
     std::memcpy(out, h_out, W);
@@ -251,47 +277,17 @@ hipMemPool_t scratch_pool(hyobfs_salamander* c) {
     return p;
 }
 
-// The launch parameters of a batch (no device call).
-int fill_params(hyobfs_salamander* c, const hyobfs_batch* b, bool obf, BatchParams& bp) {
+// The launch parameters and the plan of a batch (no device call).
+int fill_params(hyobfs_salamander* c, const hyobfs_batch* b, bool obf, BatchParams& bp, hyobfs::BatchPlan& plan) {
     if (!c || !b) return HYOBFS_ERR_INVALID;
     if (b->n && (!b->in || !b->out)) return HYOBFS_ERR_INVALID;
     if (obf && b->n && !b->salts) return HYOBFS_ERR_INVALID;
     if (reinterpret_cast<uintptr_t>(b->out) & 15) return HYOBFS_ERR_INVALID;
     if (b->out_stride > hyobfs::kMaxDatagram) return HYOBFS_ERR_INVALID;
-    bp = BatchParams{};
-    bp.n = b->n;
-    bp.in = b->in;
-    bp.in_off = b->in_off;
-    bp.in_stride = b->in_stride;
-    bp.in_len = b->in_len;
-    bp.len_uniform = b->len_uniform;
-    uint64_t cap = b->pkt_cap ? b->pkt_cap : 0;
-    if (b->out_stride && (cap == 0 || b->out_stride < cap)) cap = b->out_stride;
-    bp.pkt_cap = (uint32_t)cap;
-    bp.salts = b->salts;
-    bp.out = b->out;
-    bp.out_cap = b->out_cap;
-    bp.out_stride = b->out_stride;
-    bp.out_off = b->out_off;
-    bp.out_len = b->out_len;
-    bp.out_total = reinterpret_cast<unsigned long long*>(b->out_total);
-    bp.kernel = c->kernel.load(std::memory_order_relaxed);
+    bp = batch_params(*b, c->kernel.load(std::memory_order_relaxed));
+    plan = hyobfs::plan_batch(obf, bp);
     // device scratch: the caller's workspace, or (run_batch) the context's pool
-    const uint64_t need = hyobfs::batch_workspace_bytes(obf, bp);
-    if (need && b->workspace) {
-        if (b->workspace_bytes < need) return HYOBFS_ERR_INVALID;
-        bp.scratch = b->workspace;
-        bp.tile_sums = static_cast<uint64_t*>(b->workspace);   // (packed, explicit offsets: the tile sums)
-    }
-    return HYOBFS_OK;
-}
-
-int validate_and_fill(hyobfs_salamander* c, const hyobfs_batch* b, bool obf, BatchParams& bp,
-                      hipStream_t s) {
-    const int rc = fill_params(c, b, obf, bp);
-    if (rc != HYOBFS_OK) return rc;
-    if (b->out_total && hipMemsetAsync(b->out_total, 0, sizeof(uint64_t), s) != hipSuccess)
-        return HYOBFS_ERR_HIP;
+    if (plan.scratch_bytes && b->workspace && b->workspace_bytes < plan.scratch_bytes) return HYOBFS_ERR_INVALID;
     return HYOBFS_OK;
 }
 
@@ -301,18 +297,18 @@ int run_batch(hyobfs_salamander* c, const hyobfs_batch* b, void* stream, bool ob
     if (!g.ok) return HYOBFS_ERR_HIP;
     hipStream_t s = static_cast<hipStream_t>(stream);   // NULL = the HIP null stream
     BatchParams bp;
-    const int rc = validate_and_fill(c, b, obf, bp, s);
+    hyobfs::BatchPlan plan;
+    const int rc = fill_params(c, b, obf, bp, plan);
     if (rc != HYOBFS_OK) return rc;
+    if (b->out_total && hipMemsetAsync(b->out_total, 0, sizeof(uint64_t), s) != hipSuccess) return HYOBFS_ERR_HIP;
     void* scratch = nullptr;
-    const uint64_t need = hyobfs::batch_workspace_bytes(obf, bp);
-    if (need && !b->workspace) {   // no caller workspace: the context's pool
+    if (plan.scratch_bytes && !b->workspace) {   // no caller workspace: the context's pool
         hipMemPool_t pool = scratch_pool(c);
         if (!pool) return HYOBFS_ERR_HIP;
-        if (hipMallocFromPoolAsync(&scratch, need, pool, s) != hipSuccess) return HYOBFS_ERR_NOMEM;
+        if (hipMallocFromPoolAsync(&scratch, plan.scratch_bytes, pool, s) != hipSuccess) return HYOBFS_ERR_NOMEM;
         bp.scratch = scratch;
-        bp.tile_sums = static_cast<uint64_t*>(scratch);
     }
-    const hipError_t e = hyobfs::launch_salamander(obf, bp, c->kp, s);
+    const hipError_t e = hyobfs::launch_salamander(obf, plan, bp, c->kp, s);
     if (scratch && hipFreeAsync(scratch, s) != hipSuccess) return HYOBFS_ERR_HIP;   // after the launch, in stream order
     return hyobfs::hy_status(e);
 }
@@ -734,21 +730,10 @@ size_t hyobfs_salamander_deobfuscate(hyobfs_salamander* c, const uint8_t* in, si
 
 uint64_t hyobfs_batch_workspace_bytes(const hyobfs_batch* b) {
     if (!b) return 0;
-    hyobfs::BatchParams bp{};
-    bp.n = b->n;
-    bp.in = b->in;
-    bp.in_off = b->in_off;
-    bp.in_stride = b->in_stride;
-    bp.in_len = b->in_len;
-    bp.out_cap = b->out_cap;
-    bp.out_stride = b->out_stride;
     // the largest need over the kernel choices: independent of the context's
     uint64_t m = 0;
-    for (int k : {hyobfs::kKernelAuto, hyobfs::kKernelWave, hyobfs::kKernelFlat}) {
-        bp.kernel = k;
-        const uint64_t v = hyobfs::batch_workspace_bytes(true, bp);
-        m = v > m ? v : m;
-    }
+    for (int k : {hyobfs::kKernelAuto, hyobfs::kKernelWave, hyobfs::kKernelFlat})
+        m = std::max(m, hyobfs::plan_batch(true, batch_params(*b, k)).scratch_bytes);
     return m;
 }
 
@@ -759,8 +744,9 @@ uint64_t hyobfs_batch_workspace_size(uint64_t n) {
 
 int hyobfs_salamander_batch_kernel(hyobfs_salamander* c, const hyobfs_batch* b, int obfuscate) {
     BatchParams bp;
-    const int rc = fill_params(c, b, obfuscate != 0, bp);
-    return rc != HYOBFS_OK ? rc : hyobfs::batch_kernel(obfuscate != 0, bp);
+    hyobfs::BatchPlan plan;
+    const int rc = fill_params(c, b, obfuscate != 0, bp, plan);
+    return rc != HYOBFS_OK ? rc : plan.kernel;
 }
 
 int hyobfs_salamander_obfuscate_batch(hyobfs_salamander* c, const hyobfs_batch* b, void* stream) {

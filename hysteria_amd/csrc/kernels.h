@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 
 #include "../../include/hyobfs.h"
 #include "../../include/hyobfs_gecko.h"
@@ -54,7 +55,25 @@ struct KeyParams {
     uint32_t salt_pos;   // byte offset of salt[0] in the device blocks (0..127)
 };
 
-// One batch launch (include/hyobfs.h, struct hyobfs_batch, plus derived values).
+// The kernels that hash a salt are instantiated once per salt word SW = salt_pos / 8
+// (0..15): the PSK's message words stay scalar, only the salt's one or two words are per
+// lane.  Calls f(std::integral_constant<int, SW>) and returns its result;
+// hipErrorInvalidValue for a salt_pos of 128 or more (unreachable: make_key_params).
+template <class F, int... SW>
+hipError_t with_salt_word(uint32_t sw, F&& f, std::integer_sequence<int, SW...>) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)(... || (sw == SW && ((e = f(std::integral_constant<int, SW>{})), true)));
+    return e;
+}
+template <class F>
+hipError_t with_salt_word(const KeyParams& k, F&& f) {
+    return with_salt_word(k.salt_pos >> 3, f, std::make_integer_sequence<int, 16>{});
+}
+
+// One batch launch: the kernels' argument.  The caller of launch_salamander fills the
+// fields of include/hyobfs.h's struct hyobfs_batch, `kernel` and the one scratch pointer;
+// the derived fields (tile_prefix, tile_sums, in_tile_sums, in_tile_prefix, run_log2,
+// blk0) are written by the launchers only, on their own copy.
 struct BatchParams {
     uint64_t n;
     const uint8_t* in;
@@ -76,22 +95,56 @@ struct BatchParams {
     // lengths (scratch, ntiles+1) and their exclusive prefix (the input offsets)
     uint64_t* in_tile_sums = nullptr;
     const uint64_t* in_tile_prefix = nullptr;
-    void* scratch;                // contiguous input: the stream prepass's scratch (batch_workspace_bytes)
+    void* scratch;                // device scratch of BatchPlan::scratch_bytes bytes (unused when that is 0)
     uint32_t run_log2;            // wave kernel: datagrams per run = 2^run_log2
     uint64_t blk0 = 0;            // wave kernel, packed runs of 64: first workgroup of this launch
     int kernel;                   // HYOBFS_KERNEL_* of the context (0 = auto)
 };
 
+struct TileParams {   // the tile kernel's view of a batch (salamander_tile.h, tile_params)
+    uint32_t S;      // output slot (out_stride), a multiple of 8
+    uint32_t W;      // output width, a multiple of 8, 16 <= W <= S
+    uint32_t LI;     // input bytes per datagram (len_uniform)
+    float invS;      // 1 / S
+    uint64_t t0;     // first tile of this launch (launch_tile_sw splits big batches)
+};
+
+// What launch_salamander issues in front of the main kernel.  ntiles = ceil(n / kTile).
+enum class Prepass {
+    kNone,          // slotted output, explicit or strided input
+    kWidthScan,     // packed output, explicit or strided input: the width sums and their scan
+    kPackedScans,   // contiguous input into packed output, runs of 64: width and length sums, scanned in one launch
+    kInputOffsets,  // contiguous input into slots or shortened packed runs: length sums, their scan, the input
+                    // offsets; then an explicit-offset batch (packed: with kWidthScan's launches)
+    kFlatLocate,    // the flat kernel's: both sums, both scans, flat_locate_kernel
+};
+
+// The host's whole answer for one batch: which kernel runs, what runs in front of it, and
+// how the one scratch allocation is laid out.  plan_batch decides it; the workspace
+// query, the kernel query and launch_salamander only read it.
+struct BatchPlan {
+    int kernel;             // kKernelTile / kKernelWave / kKernelFlat; kKernelAuto: n == 0, nothing runs
+    Prepass prepass;
+    TileParams tile;        // kernel == kKernelTile
+    // byte offsets into BatchParams::scratch (a region the prepass does not use has no room there)
+    uint64_t width_sums;    // ntiles + 1 words
+    uint64_t len_sums;      // ntiles + 1 words
+    uint64_t in_off;        // kInputOffsets: n words
+    uint64_t flat_cut;      // kFlatLocate: the two cut words
+    uint64_t flat_desc;     // kFlatLocate: the tile descriptors (with the cut words flat_desc_bytes)
+    uint64_t flat_krec;     // kFlatLocate: the key records start at the next address that is a multiple of 256
+    uint64_t scratch_bytes; // the whole allocation (0: none)
+};
+// Pure (no device call): reads the batch and the process-wide knobs (HYOBFS_KERNEL,
+// HYOBFS_PACKED_RUN_LOG2), each of them read once per process.
+BatchPlan plan_batch(bool obfuscate, const BatchParams& b);
+
 // HYOBFS_KERNEL_* that a context's setting resolves to (AUTO: the
 // HYOBFS_KERNEL environment variable, else 0)
 int resolve_kernel(int ctx_kernel);
-hipError_t launch_salamander(bool obfuscate, const BatchParams& b, const KeyParams& k, hipStream_t s);
-// the kernel launch_salamander would run (kKernelTile / kKernelWave / kKernelFlat;
-// kKernelAuto for an empty batch)
-int batch_kernel(bool obfuscate, const BatchParams& b);
-// device scratch a launch of this batch needs (0: none); launch_salamander takes it
-// from b.tile_sums / b.scratch as laid out by batch_workspace_layout
-uint64_t batch_workspace_bytes(bool obfuscate, const BatchParams& b);
+// runs plan = plan_batch(obfuscate, b) on b; b.scratch holds plan.scratch_bytes bytes
+hipError_t launch_salamander(bool obfuscate, const BatchPlan& plan, const BatchParams& b, const KeyParams& k,
+                             hipStream_t s);
 // contiguous input: datagram i at in + in_len[0] + ... + in_len[i-1]
 inline bool contiguous_input(const BatchParams& b) { return !b.in_off && b.in_stride == 0 && b.in_len && b.n > 1; }
 hipError_t launch_keys(const KeyParams& k, const uint64_t* salts, uint8_t* keys, uint64_t n,

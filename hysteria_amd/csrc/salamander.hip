@@ -210,7 +210,7 @@ __global__ void synth_bimodal_kernel(uint32_t* dst, uint64_t n, uint64_t seed, u
 
 // Kernel choice ("Kernels"): AUTO runs the tile kernel where it
 // applies (tile_params) and the wave kernel elsewhere; WAVE forces the wave kernel;
-// FLAT runs the flat kernel on contiguous input into packed output (flat_eligible)
+// FLAT runs the flat kernel on contiguous input into packed output (plan_batch)
 // and is AUTO elsewhere; TILE is AUTO.  HYOBFS_KERNEL=wave|tile|flat sets what AUTO
 // means in a process.
 static int kernel_override() {   // HYOBFS_KERNEL, as HYOBFS_KERNEL_* (0 = auto); read once, thread-safe
@@ -227,36 +227,51 @@ static int kernel_override() {   // HYOBFS_KERNEL, as HYOBFS_KERNEL_* (0 = auto)
 
 int resolve_kernel(int ctx_kernel) { return ctx_kernel ? ctx_kernel : kernel_override(); }
 
-template <bool OBF, bool PACKED>
-static void launch_main(const BatchParams& bp, const KeyParams& k, hipStream_t s) {
-    const int kc = resolve_kernel(bp.kernel);
-    TileParams T;
-    if (!PACKED && kc != kKernelWave && tile_params<OBF>(bp, T)) {
-        switch (k.salt_pos >> 3) {
-#define HY_CASE(n) \
-    case n: launch_tile_sw<OBF, n>(bp, k, T, s); break;
-            HY_CASE(0) HY_CASE(1) HY_CASE(2) HY_CASE(3) HY_CASE(4) HY_CASE(5) HY_CASE(6) HY_CASE(7)
-            HY_CASE(8) HY_CASE(9) HY_CASE(10) HY_CASE(11) HY_CASE(12) HY_CASE(13) HY_CASE(14)
-            HY_CASE(15)
-#undef HY_CASE
-        }
-        return;
+// The plan of one batch (kernels.h): the one place that looks at the layout, the kernel
+// setting and the knobs.
+//   * Contiguous input into packed output from 16-byte aligned input runs the flat kernel
+//     (salamander_flat.h) when asked for (HYOBFS_KERNEL_FLAT, or HYOBFS_KERNEL=flat).  AUTO
+//     keeps the wave kernel there: on configs[2] it is faster (1.36-1.42 ms against
+//     1.53-1.68 ms for the flat kernel's variants, profiles/r06_bimodal/).
+//   * Other contiguous input into packed output in runs of 64 (the default): the wave
+//     kernel takes its input offsets from a scan of the lengths done with the widths'.
+//   * Any other contiguous input (slotted output, shorter packed runs): a prepass writes
+//     the input offsets into the scratch and the wave kernel runs on explicit offsets
+//     (never the tile kernel: the lengths are ragged).
+//   * Explicit or strided input: the tile kernel where it applies (slotted output,
+//     tile_params) unless WAVE is asked for, the wave kernel elsewhere.
+// scratch: [width sums | length sums] (ntiles + 1 words each), then the flat prepass's cut
+// words, tile descriptors and key records, or the input offsets (8 B per datagram)
+BatchPlan plan_batch(bool obf, const BatchParams& b) {
+    BatchPlan p{};   // n == 0: kKernelAuto, kNone, no scratch
+    if (b.n == 0) return p;
+    const uint64_t tsums = (div_up(b.n, kTile) + 1) * 8;
+    const int kc = resolve_kernel(b.kernel);
+    const bool packed = b.out_stride == 0;
+    p.kernel = kKernelWave;
+    p.len_sums = tsums;
+    p.in_off = p.flat_cut = 2 * tsums;
+    p.flat_desc = p.flat_cut + 16;
+    p.flat_krec = p.flat_cut + flat_desc_bytes(b.out_cap);
+    if (!contiguous_input(b)) {
+        p.prepass = packed ? Prepass::kWidthScan : Prepass::kNone;
+        p.scratch_bytes = packed ? tsums : 0;
+        if (!packed && kc != kKernelWave && (obf ? tile_params<true>(b, p.tile) : tile_params<false>(b, p.tile)))
+            p.kernel = kKernelTile;
+    } else if (packed && kc == kKernelFlat && (reinterpret_cast<uintptr_t>(b.in) & 15u) == 0) {
+        p.kernel = kKernelFlat;
+        p.prepass = Prepass::kFlatLocate;
+        p.scratch_bytes = 2 * tsums + flat_workspace_bytes(b.out_cap, b.n);
+    } else if (packed && wave_packed_run_log2() == 6) {
+        p.prepass = Prepass::kPackedScans;
+        p.scratch_bytes = 2 * tsums;
+    } else {
+        p.prepass = Prepass::kInputOffsets;
+        p.scratch_bytes = 2 * tsums + 8 * b.n;
     }
-    switch (k.salt_pos >> 3) {
-#define HY_CASE(n) \
-    case n: launch_wave_sw<OBF, PACKED, n>(bp, k, s); break;
-        HY_CASE(0) HY_CASE(1) HY_CASE(2) HY_CASE(3) HY_CASE(4) HY_CASE(5) HY_CASE(6) HY_CASE(7)
-        HY_CASE(8) HY_CASE(9) HY_CASE(10) HY_CASE(11) HY_CASE(12) HY_CASE(13) HY_CASE(14)
-        HY_CASE(15)
-#undef HY_CASE
-    }
+    return p;
 }
 
-// Contiguous input.  Packed output in runs of 64 (the default): the wave kernel takes
-// its input offsets from a scan of the lengths done with the widths'
-// (tile_sums_kernel, scan_tiles_kernel).  Otherwise (slotted output, shorter packed
-// runs) a prepass writes the input offsets into the scratch -- length sums, their
-// scan, in_offsets_kernel -- and the kernels for explicit offsets run on them.
 // A tag no earlier call used (the flat kernel's key records, salamander_flat.h): a
 // process-wide counter from a clock- and pid-derived start, never 0.
 static uint64_t next_epoch() {
@@ -269,124 +284,91 @@ static uint64_t next_epoch() {
     return e;
 }
 
-// The flat kernel (salamander_flat.h) runs when asked for (HYOBFS_KERNEL_FLAT, or
-// HYOBFS_KERNEL=flat) on contiguous input into packed output from 16-byte aligned
-// input.  AUTO keeps the wave kernel there: on configs[2] it is faster (1.36-1.42 ms
-// against 1.53-1.68 ms for the flat kernel's variants, profiles/r06_bimodal/).
-static bool flat_eligible(const BatchParams& b) {
-    return contiguous_input(b) && b.out_stride == 0 && resolve_kernel(b.kernel) == kKernelFlat &&
-           (reinterpret_cast<uintptr_t>(b.in) & 15u) == 0;
-}
-static bool wave_scans_input(const BatchParams& b) {   // the wave kernel scans the lengths itself
-    return contiguous_input(b) && b.out_stride == 0 && !flat_eligible(b) && wave_packed_run_log2() == 6;
-}
-
-// scratch: [width sums | length sums] (ntiles + 1 each), then the flat prepass's
-// header and tile descriptors, or (when the prepass writes them) the input offsets
-// (8 B per datagram)
-uint64_t batch_workspace_bytes(bool obf, const BatchParams& b) {
-    (void)obf;
-    if (b.n == 0) return 0;
-    const uint64_t tsums = (div_up(b.n, kTile) + 1) * 8;
-    if (!contiguous_input(b)) return b.out_stride == 0 ? tsums : 0;
-    if (flat_eligible(b)) return 2 * tsums + flat_workspace_bytes(b.out_cap, b.n);
-    return 2 * tsums + (wave_scans_input(b) ? 0 : 8 * b.n);
-}
-
-// Which kernel launch_salamander runs for this batch (HYOBFS_KERNEL_*; no launch).
-int batch_kernel(bool obf, const BatchParams& b) {
-    if (b.n == 0) return kKernelAuto;   // nothing runs
-    if (flat_eligible(b)) return kKernelFlat;
-    TileParams T;
-    BatchParams bp = b;
-    if (contiguous_input(b) && !wave_scans_input(b))
-        bp.in_off = reinterpret_cast<const uint64_t*>(16);   // offsets from the prepass
-    const bool tile = bp.out_stride != 0 && resolve_kernel(bp.kernel) != kKernelWave &&
-                      (obf ? tile_params<true>(bp, T) : tile_params<false>(bp, T));
-    return tile ? kKernelTile : kKernelWave;
-}
-
-template <bool OBF>
-static hipError_t launch_contiguous(BatchParams& bp, const KeyParams& k, hipStream_t s, bool& done) {
-    done = false;
-    if (!bp.scratch) return hipErrorInvalidValue;
-    const uint64_t ntiles = div_up(bp.n, kTile);
-    bp.tile_sums = static_cast<uint64_t*>(bp.scratch);
-    bp.in_tile_sums = bp.tile_sums + ntiles + 1;
-    if (flat_eligible(bp)) {   // sums, their scan, the locate prepass, the flat kernel
-        FlatParams F;
-        F.cut = bp.in_tile_sums + ntiles + 1;
-        F.desc = reinterpret_cast<FlatDesc*>(F.cut + 2);
-        F.out_total = bp.tile_sums + ntiles;     // the width scan's total
-        F.in_total = bp.in_tile_sums + ntiles;   // the length scan's total
-        F.ntiles_max = flat_ntiles_max(bp.out_cap);
-        F.krec = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(F.cut) + flat_desc_bytes(bp.out_cap) + 255) &
-                                            ~(uintptr_t)255);
-        F.epoch = next_epoch();
-        F.nhash = flat_hashers();
-        const dim3 grid((uint32_t)div_up(ntiles, 4)), block(256);
-        hipLaunchKernelGGL(tile_sums_kernel<OBF>, grid, block, 0, s, bp, ntiles);
-        hipLaunchKernelGGL(scan_tiles_kernel, dim3(2), dim3(1024), 0, s, bp.tile_sums, bp.in_tile_sums, ntiles, F.cut);
-        bp.tile_prefix = bp.tile_sums;
-        bp.in_tile_prefix = bp.in_tile_sums;
-        hipLaunchKernelGGL(flat_locate_kernel<OBF>, grid, block, 0, s, bp, F, ntiles);
-        switch (k.salt_pos >> 3) {
-#define HY_CASE(n) \
-    case n: launch_flat_sw<OBF, n>(bp, k, F, s); break;
-            HY_CASE(0) HY_CASE(1) HY_CASE(2) HY_CASE(3) HY_CASE(4) HY_CASE(5) HY_CASE(6) HY_CASE(7)
-            HY_CASE(8) HY_CASE(9) HY_CASE(10) HY_CASE(11) HY_CASE(12) HY_CASE(13) HY_CASE(14)
-            HY_CASE(15)
-#undef HY_CASE
-        }
-        done = true;
-        return hipGetLastError();
-    }
-    if (wave_scans_input(bp)) return hipSuccess;   // the packed launch below scans both sums
-    uint64_t* in_off = bp.in_tile_sums + ntiles + 1;
+// The prepass kernels that depend on the direction, by a run-time flag: for every tile of
+// kTile datagrams a wave (defined in this order, the kernels keep their order in the
+// device code object).
+static void launch_flat_locate(bool obf, const BatchParams& bp, const FlatParams& F, uint64_t ntiles, hipStream_t s) {
     const dim3 grid((uint32_t)div_up(ntiles, 4)), block(256);
-    hipLaunchKernelGGL(tile_sums_kernel<OBF>, grid, block, 0, s, bp, ntiles);
-    hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(1024), 0, s, bp.in_tile_sums, nullptr, ntiles);
-    bp.in_tile_prefix = bp.in_tile_sums;
-    hipLaunchKernelGGL(in_offsets_kernel, grid, block, 0, s, bp, in_off);
-    bp.in_off = in_off;   // from here on an ordinary batch with explicit offsets
-    bp.in_tile_sums = nullptr;
-    bp.in_tile_prefix = nullptr;
-    return hipGetLastError();
+    if (obf)
+        hipLaunchKernelGGL(flat_locate_kernel<true>, grid, block, 0, s, bp, F, ntiles);
+    else
+        hipLaunchKernelGGL(flat_locate_kernel<false>, grid, block, 0, s, bp, F, ntiles);
+}
+static void launch_tile_sums(bool obf, const BatchParams& bp, uint64_t ntiles, hipStream_t s) {
+    const dim3 grid((uint32_t)div_up(ntiles, 4)), block(256);
+    if (obf)
+        hipLaunchKernelGGL(tile_sums_kernel<true>, grid, block, 0, s, bp, ntiles);
+    else
+        hipLaunchKernelGGL(tile_sums_kernel<false>, grid, block, 0, s, bp, ntiles);
 }
 
-hipError_t launch_salamander(bool obf, const BatchParams& b, const KeyParams& k, hipStream_t s) {
+// Executes a plan: its prepass, then its kernel, on a copy of the batch whose derived
+// fields point into the scratch.  The plan's offsets are resolved here and nowhere else.
+template <bool OBF>
+static hipError_t run_plan(const BatchPlan& p, BatchParams bp, const KeyParams& k, hipStream_t s) {
+    const uint64_t ntiles = div_up(bp.n, kTile);
+    uint8_t* const base = static_cast<uint8_t*>(bp.scratch);
+    auto words = [base](uint64_t off) { return reinterpret_cast<uint64_t*>(base + off); };
+    FlatParams F{};
+    if (p.prepass != Prepass::kNone) bp.tile_sums = words(p.width_sums);
+    if (p.prepass != Prepass::kNone && p.prepass != Prepass::kWidthScan) bp.in_tile_sums = words(p.len_sums);
+    switch (p.prepass) {
+        case Prepass::kNone: break;
+        case Prepass::kFlatLocate:
+            F.cut = words(p.flat_cut);
+            F.desc = reinterpret_cast<FlatDesc*>(base + p.flat_desc);
+            F.out_total = bp.tile_sums + ntiles;     // the width scan's total
+            F.in_total = bp.in_tile_sums + ntiles;   // the length scan's total
+            F.ntiles_max = flat_ntiles_max(bp.out_cap);
+            F.krec = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(base + p.flat_krec) + 255) & ~(uintptr_t)255);
+            F.epoch = next_epoch();
+            F.nhash = flat_hashers();
+            launch_tile_sums(OBF, bp, ntiles, s);
+            hipLaunchKernelGGL(scan_tiles_kernel, dim3(2), dim3(1024), 0, s, bp.tile_sums, bp.in_tile_sums, ntiles, F.cut);
+            bp.tile_prefix = bp.tile_sums;
+            bp.in_tile_prefix = bp.in_tile_sums;
+            launch_flat_locate(OBF, bp, F, ntiles, s);
+            break;
+        case Prepass::kInputOffsets:
+            launch_tile_sums(OBF, bp, ntiles, s);
+            hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(1024), 0, s, bp.in_tile_sums, nullptr, ntiles);
+            bp.in_tile_prefix = bp.in_tile_sums;
+            hipLaunchKernelGGL(in_offsets_kernel, dim3((uint32_t)div_up(ntiles, 4)), dim3(256), 0, s, bp, words(p.in_off));
+            bp.in_off = words(p.in_off);   // from here on an ordinary batch with explicit offsets
+            bp.in_tile_sums = nullptr;
+            bp.in_tile_prefix = nullptr;
+            if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+            if (bp.out_stride != 0) break;
+            [[fallthrough]];   // packed: that batch's width sums
+        case Prepass::kWidthScan:
+        case Prepass::kPackedScans:
+            launch_tile_sums(OBF, bp, ntiles, s);
+            hipLaunchKernelGGL(scan_tiles_kernel, dim3(bp.in_tile_sums ? 2 : 1), dim3(1024), 0, s, bp.tile_sums,
+                               bp.in_tile_sums, ntiles);
+            bp.tile_prefix = bp.tile_sums;
+            bp.in_tile_prefix = bp.in_tile_sums;
+            break;
+    }
+    return with_salt_word(k, [&](auto sw) {
+        constexpr int SW = decltype(sw)::value;
+        if (p.kernel == kKernelTile)
+            launch_tile_sw<OBF, SW>(bp, k, p.tile, s);
+        else if (p.kernel == kKernelFlat)
+            launch_flat_sw<OBF, SW>(bp, k, F, s);
+        else if (bp.out_stride == 0)
+            launch_wave_sw<OBF, true, SW>(bp, k, s);
+        else
+            launch_wave_sw<OBF, false, SW>(bp, k, s);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_salamander(bool obf, const BatchPlan& p, const BatchParams& b, const KeyParams& k, hipStream_t s) {
     if (b.n == 0) return hipSuccess;
-    const uint64_t ntiles = div_up(b.n, kTile);
-    if (ntiles > 0x7fffffffull) return hipErrorInvalidValue;
+    if (div_up(b.n, kTile) > 0x7fffffffull) return hipErrorInvalidValue;
     if (k.nblk == 2 && (k.salt_pos >> 3) != 15) return hipErrorInvalidValue;   // by construction
-    BatchParams bp = b;
-    if (contiguous_input(b)) {
-        bool done = false;
-        const hipError_t e = obf ? launch_contiguous<true>(bp, k, s, done) : launch_contiguous<false>(bp, k, s, done);
-        if (e != hipSuccess || done) return e;
-    }
-    if (bp.out_stride == 0) {
-        if (!bp.tile_sums) return hipErrorInvalidValue;
-        const dim3 grid((uint32_t)div_up(ntiles, 4)), block(256);
-        if (obf)
-            hipLaunchKernelGGL(tile_sums_kernel<true>, grid, block, 0, s, bp, ntiles);
-        else
-            hipLaunchKernelGGL(tile_sums_kernel<false>, grid, block, 0, s, bp, ntiles);
-        hipLaunchKernelGGL(scan_tiles_kernel, dim3(bp.in_tile_sums ? 2 : 1), dim3(1024), 0, s, bp.tile_sums,
-                           bp.in_tile_sums, ntiles);
-        bp.tile_prefix = bp.tile_sums;
-        bp.in_tile_prefix = bp.in_tile_sums;
-        if (obf)
-            launch_main<true, true>(bp, k, s);
-        else
-            launch_main<false, true>(bp, k, s);
-    } else {
-        if (obf)
-            launch_main<true, false>(bp, k, s);
-        else
-            launch_main<false, false>(bp, k, s);
-    }
-    return hipGetLastError();
+    if (p.scratch_bytes && !b.scratch) return hipErrorInvalidValue;
+    return obf ? run_plan<true>(p, b, k, s) : run_plan<false>(p, b, k, s);
 }
 
 hipError_t launch_keys(const KeyParams& k, const uint64_t* salts, uint8_t* keys, uint64_t n,

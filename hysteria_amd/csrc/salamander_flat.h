@@ -36,7 +36,7 @@
 //        byte-masked).
 // A tile reached by more than kFD datagrams takes several passes of 2-3; a chunk two
 // passes share gets each pass's bytes by a byte-masked store.  Applies to contiguous input with packed
-// output and 16-byte aligned `in` and `out` (flat_eligible, salamander.hip); the wave
+// output and 16-byte aligned `in` and `out` (plan_batch, salamander.hip); the wave
 // kernel takes every other packed layout.
 #pragma once
 #include "salamander_tile.h"

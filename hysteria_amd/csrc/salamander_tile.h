@@ -32,14 +32,6 @@ constexpr uint64_t kMaxTileSlot = 1u << 20;
 #define HY_TILE_MIN_WAVES 8
 #endif
 
-struct TileParams {
-    uint32_t S;      // output slot (out_stride), a multiple of 8
-    uint32_t W;      // output width, a multiple of 8, 16 <= W <= S
-    uint32_t LI;     // input bytes per datagram (len_uniform)
-    float invS;      // 1 / S
-    uint64_t t0;     // first tile of this launch (launch_tile_sw splits big batches)
-};
-
 #ifndef HY_TILE_SU
 #define HY_TILE_SU 5             // staged: output chunks per thread and pass (256 x 5 x 16 B = 20 KiB)
 #endif
