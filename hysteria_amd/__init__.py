@@ -3,7 +3,7 @@
 The product is ``libhyobfs.so`` (gfx950 HIP kernels behind the C ABI of
 ``include/hyobfs.h``); this package is its Python host binding.
 """
-from . import acl, addr, gecko, sniff, udpmsg  # noqa: F401
+from . import acl, addr, gecko, request, sniff, udpmsg  # noqa: F401
 from .acl import (  # noqa: F401
     ACL_RESULT_DTYPE,
     CompilationError,
@@ -15,6 +15,7 @@ from .acl import (  # noqa: F401
     quic_sniff_and_match,
 )
 from .addr import AddrError, relay_acl_decisions  # noqa: F401
+from .request import PortSet, RequestError, hooked_relay_acl_decisions, tcp_request_decisions  # noqa: F401
 from .conn import SalamanderPacketConn, wrap_packet_conn_salamander  # noqa: F401
 from .gecko import GeckoOptions, GeckoPacketConn, GeckoReceiver, wrap_packet_conn_gecko  # noqa: F401
 from .salamander import (  # noqa: F401
@@ -68,5 +69,6 @@ __all__ = [
     "InvalidSyntaxError", "RuleSet", "TextRule", "compile_rules", "parse_text_rules", "quic_sniff_and_match",
     "http_request_host_batch", "tcp_sniff_batch", "BATCH_MAX_DATAGRAM", "udpmsg", "UDPMessage", "UDPMessageError",
     "parse_udp_message", "frag_udp_message", "Defragger", "relay_quic_snis", "UDP_PARSED_DTYPE", "UDP_META_DTYPE",
-    "GeckoReceiver", "addr", "AddrError", "relay_acl_decisions",
+    "GeckoReceiver", "addr", "AddrError", "relay_acl_decisions", "request", "PortSet", "RequestError",
+    "tcp_request_decisions", "hooked_relay_acl_decisions",
 ]

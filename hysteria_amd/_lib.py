@@ -161,6 +161,27 @@ _ADDR_SIG = {   # include/hyobfs_addr.h (hysteria_amd/addr.py); declared by load
     "hyobfs_addr_format_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
 }
 
+_i64p, _u32p, _u8p = ctypes.POINTER(_i64), ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_uint8)
+_REQ_SIG = {   # include/hyobfs_request.h (hysteria_amd/request.py); declared by load() like the ACL's
+    "hyobfs_tcp_request_parse": (_i32, [_vp, _sz, _u32p, _u32p, _u32p, _u32p]),
+    "hyobfs_tcp_request_build": (_i64, [_vp, _sz, _u32, _u64, _u64, _vp, _sz]),
+    "hyobfs_tcp_response_parse": (_i32, [_vp, _sz, _u32p, _u8p, _u32p, _u32p, _u32p]),
+    "hyobfs_tcp_response_build": (_i64, [_i32, _vp, _sz, _u32, _u64, _u64, _vp, _sz]),
+    "hyobfs_req_padding_fill": (None, [_u64, _u64, _vp, _sz]),
+    "hyobfs_port_union_parse": (_i32, [_vp, _sz, _vp, _u32, _u32p]),
+    "hyobfs_port_union_contains": (_i32, [_vp, _i64, ctypes.c_uint16]),
+    "hyobfs_sniff_check": (_i32, [_vp, _sz, _i32, _i32, _vp, _i64, _vp, _i64]),
+    "hyobfs_request_rewrite": (_i64, [_vp, _sz, _i32, _vp, _sz, _i32, _vp, _sz, _u8p]),
+    "hyobfs_portset_new": (_i32, [_vp, _u32, _i32, ctypes.POINTER(_vp)]),
+    "hyobfs_portset_free": (None, [_vp]),
+    "hyobfs_tcp_request_parse_batch": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hyobfs_sniff_check_batch": (_i32, [_vp, _vp, _vp, _vp, _u64, _i32, _i32, _vp, _vp, _vp]),
+    "hyobfs_request_rewrite_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u64, _vp, _u64, _u64, _vp, _vp,
+                                            _vp, _vp, _vp]),
+    "hyobfs_tcp_response_build_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _u64, _u64, _vp, _u64, _vp, _vp,
+                                               _vp]),
+}
+
 _lib = None
 _variants = {}   # other builds loaded side by side (in-process A/B runs, scripts/ab_variants.py)
 
@@ -200,6 +221,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         declare(lib, "udpmsg", _UDP_SIG)
     if hasattr(lib, "hyobfs_addr_parse_batch"):   # likewise addr.hip / addr_host.cpp (addr._adlib())
         declare(lib, "addr", _ADDR_SIG)
+    if hasattr(lib, "hyobfs_tcp_request_parse_batch"):   # likewise request.hip / request_host.cpp (request._rqlib())
+        declare(lib, "request", _REQ_SIG)
     have = lib.hyobfs_abi_version()
     if have != ABI_VERSION:   # struct layouts and enum values differ between versions
         raise OSError(f"{path}: ABI version {have}, these bindings need {ABI_VERSION}: rebuild the library")

@@ -24,6 +24,7 @@
 
 #include "../../include/hyobfs.h"
 #include "../../include/hyobfs_addr.h"
+#include "../../include/hyobfs_request.h"
 #include "conn_coalesce.h"
 #include "kernels.h"
 
@@ -503,6 +504,14 @@ const char* hyobfs_status_string(int st) {
         case HYOBFS_ADDR_ERR_PORT: return "invalid port";
         case HYOBFS_ADDR_ERR_TOO_LONG: return "address too long";
         case HYOBFS_ADDR_ERR_FAMILY: return "address family is neither 4 nor 16";
+        case HYOBFS_REQ_ERR_NEED_MORE: return "the frame is not complete yet";
+        case HYOBFS_REQ_ERR_ADDR_LEN: return "invalid address length";
+        case HYOBFS_REQ_ERR_PADDING_LEN: return "invalid padding length";
+        case HYOBFS_REQ_ERR_MSG_LEN: return "invalid message length";
+        case HYOBFS_REQ_ERR_CAP: return "the output row is too short";
+        case HYOBFS_REQ_ERR_NO_ADDR: return "the request has no address";
+        case HYOBFS_REQ_ERR_HOST: return "left to the host: the sniffer has no answer yet";
+        case HYOBFS_REQ_ERR_UNION: return "invalid port union";
         default: return "unknown status";
     }
 }

@@ -29,9 +29,9 @@
  * STAYS WITH THE CALLER
  *   - DNS resolution: a host that is no IP literal gets no address here; the
  *     caller's resolver may overlay ipv4 / ipv6 / ip_flags afterwards.
- *   - Sniffer.Check (extras/sniff/sniff.go:67-89): it uses strconv.Atoi, which
- *     accepts a sign, and a port union.
  *   - The "@" internal addresses: "@SpeedTest" is simply MISSING_PORT here.
+ *     (Sniffer.Check, which tests for them, uses strconv.Atoi and has a port
+ *     union, and the rewrite of the address are hyobfs_request.h's.)
  *   - The per-session ACL decision cache.
  *   - The SOCKS5 address form of ob_socks5.go.
  *

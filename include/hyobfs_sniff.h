@@ -18,7 +18,10 @@
  *   (*Sniffer).TCP, the whole dispatch    sniff.go:103-156 hyobfs_tcp_sniff_batch (device)
  *
  * What the sniffer does with the name (Check, SplitHostPort / JoinHostPort on
- * the request address) stays on the host: hysteria_amd/sniff.py shows it.
+ * the request address) is hyobfs_request.h: hyobfs_sniff_check_batch decides
+ * which requests are sniffed and hyobfs_request_rewrite_batch takes `names` and
+ * the results of the calls below as they are.  hysteria_amd/sniff.py keeps the
+ * host's version of it.
  *
  * THE PARSE RULES.  utls forks Go's crypto/tls clientHelloMsg.unmarshal.  Its
  * source was not at hand when this was written, so the rules below, restated
