@@ -23,12 +23,19 @@ the matchers (matchers.go, matchers_v2geo.go)       ``include/hyobfs_acl.h`` sta
 ==================================================  ==================================================
 
 Matching runs in ``libhyobfs.so`` (``include/hyobfs_acl.h`` states the rules and
-the one divergence).  The device leaves three kinds of names to the host (a byte
+the one divergence).  A geosite entry of type regex goes to the device only on
+request (``compile_rules(..., device_regex=True)``) and only if the library takes
+its pattern (``regex_check``; the header's "THE REGEX SUBSET"); without the
+switch such an entry is a CompilationError, as before.  The device leaves three kinds of names to the host (a byte
 >= 0x80, ``xn--`` anywhere, more than 255 bytes), because ``domainMatcher`` runs
 ``idna.ToUnicode`` on the name; ``match_many`` finishes exactly those items with
 ``RuleSet.match_host``, which decodes ``xn--`` labels with the standard
 library's punycode codec and keeps the undecoded name on any error.  That is the
-one CPU path, and only for those names.
+one CPU path, and only for those names.  It evaluates a regex entry with ``re``
+under ``re.ASCII`` on the decoded name, after the translation that Go's
+semantics demand (``_regex_to_py``).  STATED DIVERGENCE: a name that is not valid
+UTF-8 is decoded with U+FFFD in place of each invalid sequence as Python
+delimits it; Go walks such bytes as one U+FFFD rune per byte.
 
 Out of scope: reading geoip / geosite ``.dat`` files (``geo`` hands the lists
 over), the outbounds themselves, the resolver, and the LRU cache of
@@ -48,13 +55,15 @@ from ._dev import _pack, _ptr, _records, _stream, _to
 
 MAX_NAME = 255
 NO_HIJACK = 0xFFFFFFFF
+FLAG_REGEX = 1              # HYOBFS_ACL_FLAG_REGEX
+REGEX_MAX_STATES = 4096     # HYOBFS_ACL_REGEX_MAX_STATES
 PROTO_BOTH, PROTO_TCP, PROTO_UDP = 0, 1, 2
 
 ERR_NO_NAME, ERR_HOST, ERR_REGEX, ERR_PATTERN = range(-61, -65, -1)
 ERRORS = {
     ERR_NO_NAME: "no sniffed name",
     ERR_HOST: "name left to the host",
-    ERR_REGEX: "a regex entry cannot be matched on the device",
+    ERR_REGEX: "a regex entry cannot be matched on the device",   # not asked for, or outside the subset
     ERR_PATTERN: "pattern longer than 255 bytes",
 }
 
@@ -96,22 +105,28 @@ def _alib(lib=None):
 
 # ------------------------------------------------------------------ device calls
 class RuleRefused(ValueError):
-    """hyobfs_acl_ruleset_new refused rule ``rule`` with ``status``."""
+    """hyobfs_acl_ruleset_new refused rule ``rule`` with ``status``; ``entry``: the
+    DOMAIN_SET entry it was about, or -1."""
 
-    def __init__(self, status: int, rule: int):
-        self.status, self.rule = status, rule
-        super().__init__(f"rule {rule}: {ERRORS.get(status, 'invalid rule')} ({status})")
+    def __init__(self, status: int, rule: int, entry: int = -1):
+        self.status, self.rule, self.entry = status, rule, entry
+        where = f"rule {rule}" + (f", entry {entry}" if entry >= 0 else "")
+        super().__init__(f"{where}: {ERRORS.get(status, 'invalid rule')} ({status})")
 
 
-def ruleset_new(c_rules, n_rules: int, device: int = 0):
-    """hyobfs_acl_ruleset_new over a HyobfsAclRule array: the handle.  A refused
-    rule raises RuleRefused (before the device is looked at)."""
+def ruleset_new(c_rules, n_rules: int, device: int = 0, flags: int = 0):
+    """hyobfs_acl_ruleset_new (``flags`` == 0) or hyobfs_acl_ruleset_new_flags over a
+    HyobfsAclRule array: the handle.  A refused rule raises RuleRefused (before
+    the device is looked at)."""
     lib = _alib()
     h = ctypes.c_void_p()
-    st = lib.hyobfs_acl_ruleset_new(c_rules, n_rules, device, ctypes.byref(h))
+    if flags:
+        st = lib.hyobfs_acl_ruleset_new_flags(c_rules, n_rules, device, flags, ctypes.byref(h))
+    else:
+        st = lib.hyobfs_acl_ruleset_new(c_rules, n_rules, device, ctypes.byref(h))
     bad = int(lib.hyobfs_acl_ruleset_bad_rule())
     if st != _lib.HYOBFS_OK and bad >= 0:
-        raise RuleRefused(st, bad)
+        raise RuleRefused(st, bad, int(lib.hyobfs_acl_ruleset_bad_entry()))
     _lib.check(st, "acl_ruleset_new")
     assert lib.hyobfs_acl_ruleset_rules(h) == n_rules
     return h
@@ -119,6 +134,30 @@ def ruleset_new(c_rules, n_rules: int, device: int = 0):
 
 def ruleset_free(handle) -> None:
     _alib().hyobfs_acl_ruleset_free(handle)
+
+
+def _pattern_bytes(p) -> bytes:
+    return p.encode("utf-8", "surrogateescape") if isinstance(p, str) else bytes(p)
+
+
+def regex_check(pattern):
+    """hyobfs_acl_regex_check (host only): (status, DFA states, byte classes) of a
+    geosite regex value; status 0 when the device takes it, else ERR_REGEX or
+    ERR_PATTERN with zeros."""
+    p = _pattern_bytes(pattern)
+    states, classes = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    st = _alib().hyobfs_acl_regex_check(p, len(p), ctypes.byref(states), ctypes.byref(classes))
+    return int(st), int(states.value), int(classes.value)
+
+
+def regex_match(pattern, name) -> bool:
+    """hyobfs_acl_regex_match (host only): the kernel's DFA walk of ``pattern`` over
+    the bytes of ``name`` as given.  A refused pattern raises ValueError."""
+    p, n = _pattern_bytes(pattern), _pattern_bytes(name)
+    st = _alib().hyobfs_acl_regex_match(p, len(p), n, len(n))
+    if st < 0:
+        raise ValueError(f"regex {pattern!r}: {ERRORS.get(st, 'invalid')} ({st})")
+    return bool(st)
 
 
 def match_batch(handle, names, name_off, name_len, ipv4, ipv6, ip_flags, proto, port, n: int, res, stream=None) -> None:
@@ -253,9 +292,10 @@ class Rule:
         self.hijack = None
 
 
-def compile_host_matcher(addr: str, geo=None) -> Rule:
+def compile_host_matcher(addr: str, geo=None, device_regex: bool = False) -> Rule:
     """compileHostMatcher (compile.go:235-316), its tests in the reference's
-    order.  Raises ValueError with the reference's message."""
+    order.  Raises ValueError with the reference's message.  ``device_regex``: a
+    geosite regex entry is kept if the library takes its pattern."""
     addr = addr.lower().rstrip(".")
     if addr in ("*", "all"):
         return Rule(KIND_ALL)
@@ -298,7 +338,12 @@ def compile_host_matcher(addr: str, geo=None) -> Rule:
             if attrs and not all(a in have for a in attrs):
                 continue
             if typ == "regex":
-                raise ValueError(f"GeoSite name {name}: regex entry {value!r} cannot be matched on the device")
+                if not device_regex:
+                    raise ValueError(f"GeoSite name {name}: regex entry {value!r} cannot be matched on the device")
+                st = regex_check(value)[0]
+                if st != _lib.HYOBFS_OK:
+                    raise ValueError(f"GeoSite name {name}: regex entry {value!r}: "
+                                     f"{ERRORS.get(st, 'invalid pattern')} ({st})")
             entries.append((typ, value))
         return Rule(KIND_DOMAIN_SET, entries=entries)
     if addr.startswith("suffix:"):
@@ -318,19 +363,21 @@ def compile_host_matcher(addr: str, geo=None) -> Rule:
     return Rule(KIND_DOMAIN_EXACT, pattern=addr)
 
 
-def compile_rules(text_rules, outbounds: dict, geo=None) -> "RuleSet":
+def compile_rules(text_rules, outbounds: dict, geo=None, device_regex: bool = False) -> "RuleSet":
     """Compile (compile.go:130-161).  ``outbounds`` maps lower-case names to
     integers; ``geo`` (optional) has ``geoip(code)`` returning a list of (address
     bytes, prefix) -- or (that list, inverse) -- and ``geosite(name)`` returning a
     list of (type, value, attributes) with type "plain", "regex", "root" or
     "full"; both return None for an unknown name.  A regex entry that passes the
-    rule's attribute filter is a CompilationError: the device cannot match it."""
+    rule's attribute filter is a CompilationError, unless ``device_regex`` is set:
+    then it is kept and matched on the device, and only a pattern that
+    ``regex_check`` refuses is a CompilationError, with the library's status."""
     rules = []
     for tr in text_rules:
         if tr.outbound.lower() not in outbounds:
             raise CompilationError(tr.line_num, f"outbound {tr.outbound} not found")
         try:
-            rule = compile_host_matcher(tr.address, geo)
+            rule = compile_host_matcher(tr.address, geo, device_regex)
         except ValueError as e:
             raise CompilationError(tr.line_num, str(e)) from None
         for what, p in (("pattern", rule.pattern), *(("value", e[1]) for e in rule.entries
@@ -416,6 +463,75 @@ def _wildcard(name: str, pattern: str) -> bool:
     return all(c == "*" for c in pattern[q:])
 
 
+_GO_SPACE = frozenset(b"\t\n\f\r ")   # Go's \s: no \v (Python's has it)
+_PERL = {"d": frozenset(range(0x30, 0x3A)), "s": _GO_SPACE,
+         "w": frozenset(b"0123456789_abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ")}
+
+
+def _py_class(ascii_set, beyond: bool) -> str:
+    """A character class of exactly these ASCII code points, and every code point
+    beyond ASCII if ``beyond``."""
+    inside = sorted(set(range(128)) - ascii_set) if beyond else sorted(ascii_set)
+    if not inside:
+        return "[\\x00-\\U0010ffff]" if beyond else "(?!)"
+    return "[%s%s]" % ("^" if beyond else "", "".join("\\x%02x" % c for c in inside))
+
+
+def _regex_to_py(pattern: str) -> str:
+    """A geosite regex (Go syntax, the header's subset) as a Python pattern for
+    ``re.ASCII`` with Go's meaning: ``^`` -> ``\\A``, ``$`` -> ``\\Z`` (Python's ``$`` also
+    matches before a trailing newline), ``\\s`` / ``\\S`` and every class spelled out
+    (Go's ``\\s`` has no ``\\v``)."""
+    out, i, n = [], 0, len(pattern)
+    while i < n:
+        c = pattern[i]
+        i += 1
+        if c == "\\" and i < n:
+            e = pattern[i]
+            i += 1
+            if e in "sS":
+                out.append(_py_class(set(_GO_SPACE), False) if e == "s" else _py_class(set(range(128)) - _GO_SPACE, True))
+            else:
+                out.append("\\" + e)
+        elif c == "^":
+            out.append("\\A")
+        elif c == "$":
+            out.append("\\Z")
+        elif c == "[":
+            neg = i < n and pattern[i] == "^"
+            i += neg
+            members, beyond = set(), False
+
+            def member():
+                """One class member at i: (ASCII set, reaches beyond ASCII, is a single byte)."""
+                nonlocal i
+                ch = pattern[i]
+                i += 1
+                if ch != "\\":
+                    return {ord(ch)}, False, True
+                e = pattern[i]
+                i += 1
+                if e.lower() in _PERL and e.isalpha():
+                    s = set(_PERL[e.lower()])
+                    return (s, False, False) if e.islower() else (set(range(128)) - s, True, False)
+                return {ord(e)}, False, True
+            while i < n and pattern[i] != "]":
+                s, b, single = member()
+                if single and i + 1 < n and pattern[i] == "-" and pattern[i + 1] != "]":
+                    i += 1
+                    hi = member()[0]
+                    s = set(range(min(s), max(hi) + 1))
+                members |= s
+                beyond |= b
+            i += 1   # the ']'
+            if neg:
+                members, beyond = set(range(128)) - members, not beyond
+            out.append(_py_class(members, beyond))
+        else:
+            out.append(c)
+    return "".join(out)
+
+
 def _as_ip(x, size):
     """None, bytes of ``size``, an ipaddress object or its text -> bytes or None."""
     if x is None:
@@ -441,6 +557,7 @@ class RuleSet:
         self.rules = list(rules)
         self.hijacks = sorted({r.hijack for r in self.rules if r.hijack is not None})
         self._sets = {}
+        self._regexes = {}   # pattern -> compiled, for match_host
 
     def __len__(self):
         return len(self.rules)
@@ -464,7 +581,8 @@ class RuleSet:
         if r.kind == KIND_DOMAIN_SET:
             for typ, value in r.entries:
                 if (typ == "plain" and value in name) or (typ == "full" and name == value) or \
-                        (typ == "root" and (name == value or name.endswith("." + value))):
+                        (typ == "root" and (name == value or name.endswith("." + value))) or \
+                        (typ == "regex" and self._regex(value).search(name) is not None):
                     return True
             return False
         # KIND_CIDR_SET: geoipMatcher.Match with the reference's binary search
@@ -485,6 +603,11 @@ class RuleSet:
                 else:
                     right = mid - 1
         return bool(r.inverse)
+
+    def _regex(self, value: str):
+        if value not in self._regexes:
+            self._regexes[value] = re.compile(_regex_to_py(value), re.ASCII)
+        return self._regexes[value]
 
     def match_host(self, name, ipv4=None, ipv6=None, proto: int = 0, port: int = 0) -> int:
         """compiledRuleSetImpl.Match (compile.go:88-109) on the CPU: the index of the
@@ -511,7 +634,8 @@ class RuleSet:
 
     # -- device side
     def c_rules(self):
-        """(hyobfs_acl_rule array, the buffers it points into)."""
+        """(hyobfs_acl_rule array, the buffers it points into).  A regex entry is handed
+        over as it is: hyobfs_acl_ruleset_new_flags with ``flags()`` takes it."""
         keep = []
 
         def buf(b):
@@ -544,12 +668,18 @@ class RuleSet:
                 c.entries, c.n_entries, c.inverse = ctypes.cast(ents, ctypes.c_void_p), len(r.entries), int(r.inverse)
         return arr, keep
 
+    def flags(self) -> int:
+        """HYOBFS_ACL_FLAG_REGEX if a rule holds a regex entry, else 0."""
+        return FLAG_REGEX if any(r.kind == KIND_DOMAIN_SET and any(e[0] == "regex" for e in r.entries)
+                                 for r in self.rules) else 0
+
     def device_set(self, device: int = 0):
-        """The hyobfs_acl_ruleset handle on cuda:<device> (made once)."""
+        """The hyobfs_acl_ruleset handle on cuda:<device> (made once); regex entries
+        go over with HYOBFS_ACL_FLAG_REGEX."""
         if device not in self._sets:
             arr, keep = self.c_rules()
             try:
-                self._sets[device] = ruleset_new(arr, len(self.rules), device)
+                self._sets[device] = ruleset_new(arr, len(self.rules), device, self.flags())
             except RuleRefused as e:
                 line = self.rules[e.rule].line_num if 0 <= e.rule < len(self.rules) else 0
                 raise CompilationError(line, str(e)) from None

@@ -20,8 +20,11 @@
 // The entry table: a rule of any kind but the two sets is one 32-byte entry; a
 // DOMAIN_SET is one entry per value (FULL as an exact entry, ROOT as a suffix
 // entry, PLAIN as a substring entry); a CIDR_SET is one entry whose lane runs
-// the reference's binary search.  A domain entry carries the end of its pattern
-// (16 bytes) next to its lengths, and the wave keeps the end of its name in
+// the reference's binary search.  A REGEX value of a DOMAIN_SET is one entry too:
+// its lane walks the value's DFA (acl_regex.h) over the name in LDS, and a rule's
+// regex entries stand together after its other entries, so that their walks run
+// side by side in as few steps as possible.  A domain entry carries the end of its
+// pattern (16 bytes) next to its lengths, and the wave keeps the end of its name in
 // registers, so all but a near miss is decided without touching the pattern
 // bytes in memory.  Addresses are kept as four big-endian words
 // in v4-mapped form, so Equal and Contains with their To4 rules become word
@@ -31,6 +34,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "acl_regex.h"
 #include "../../include/hyobfs_acl.h"
 
 namespace hyobfs {
@@ -46,12 +50,13 @@ constexpr uint32_t kWaves = 4;   // items per workgroup
 constexpr uint32_t kGridCap = HY_ACL_GRID_CAP;
 constexpr uint32_t kNameLds = 256;   // HYOBFS_ACL_MAX_NAME rounded up to whole rounds of 64 lanes
 
-enum : uint32_t { kAll = 0, kIp, kCidr4, kCidr6, kExact, kWildcard, kSuffix, kPlain, kCidrSet };
+enum : uint32_t { kAll = 0, kIp, kCidr4, kCidr6, kExact, kWildcard, kSuffix, kPlain, kCidrSet, kRegex };
 enum { kBatch = 0, kSniffed = 1 };
 
 struct alignas(16) Entry {
     uint32_t rule;
-    uint32_t off;    // pattern: byte offset in `pats`; address / CIDR set: word offset in `words`
+    uint32_t off;    // pattern: byte offset in `pats`; address / CIDR set: word offset in `words`;
+                     // kRegex: cell offset in `dfa`
     uint16_t len;    // pattern length; kCidr4 / kCidr6: leading bits of the 128 that must agree
     uint8_t kind, proto;
     uint16_t start_port, end_port;
@@ -62,6 +67,7 @@ struct alignas(16) Entry {
     //                     of them, the last one first; word 3: the shortest name the pattern
     //                     takes (len less its stars) | that count of literal bytes << 16
     //   kPlain            word 0: the first min(len, 4) bytes of the value, in order
+    //   kRegex            word 0: the start state (0, rx::kAccept or rx::kDead)
     uint32_t tail[4];
 };
 static_assert(sizeof(Entry) == 32, "Entry layout");
@@ -76,6 +82,7 @@ struct Args {
     const RuleOut* rule_out;
     const uint32_t* words;
     const uint8_t* pats;
+    const uint16_t* dfa;
     uint32_t n_entries;
     const uint8_t* names;
     const uint64_t* name_off;          // kBatch
@@ -247,6 +254,8 @@ HY_HD bool entry_matches(const Entry& e, const Args& a, const uint8_t* name, uin
             if (!found && h.has_b) found = cidr_set_has(s, h.b, h.b4);
             return found != (s[2] != 0);
         }
+        case kRegex:
+            return rx::walk(a.dfa + e.off, e.tail[0], name, nl);
         default:
             return false;
     }
@@ -377,7 +386,10 @@ struct Tables {
     std::vector<RuleOut> rule_out;
     std::vector<uint32_t> words;
     std::vector<uint8_t> pats;
+    std::vector<uint16_t> dfa;
 };
+
+thread_local int64_t t_bad_rule = -1, t_bad_entry = -1;
 
 inline bool v4_mapped(const uint8_t* a) {
     static const uint8_t pre[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0xFF, 0xFF};
@@ -420,7 +432,7 @@ inline int add_pattern(Tables& t, Entry e, uint32_t kind, const uint8_t* p, uint
 }
 
 // One compiledRule into the tables; a status other than OK refuses the rule.
-int add_rule(Tables& t, const hyobfs_acl_rule& r, uint32_t index) {
+int add_rule(Tables& t, const hyobfs_acl_rule& r, uint32_t index, uint32_t flags) {
     if (r.kind > HYOBFS_ACL_CIDR_SET || r.proto > 2) return HYOBFS_ERR_INVALID;
     t.rule_out.push_back(RuleOut{r.outbound, r.hijack});
     Entry e{};
@@ -465,8 +477,25 @@ int add_rule(Tables& t, const hyobfs_acl_rule& r, uint32_t index) {
         case HYOBFS_ACL_DOMAIN_SET: {
             if (!r.entries && r.n_entries) return HYOBFS_ERR_INVALID;
             const auto* d = static_cast<const hyobfs_acl_domain*>(r.entries);
+            // the regex entries after the others (the set's result does not depend on the order)
+            std::vector<Entry> regexes;
             for (uint32_t k = 0; k < r.n_entries; ++k) {
-                if (d[k].type == HYOBFS_ACL_DOMAIN_REGEX) return HYOBFS_ACL_ERR_REGEX;
+                t_bad_entry = k;
+                if (d[k].type == HYOBFS_ACL_DOMAIN_REGEX) {
+                    if (!(flags & HYOBFS_ACL_FLAG_REGEX)) return HYOBFS_ACL_ERR_REGEX;
+                    if (d[k].len > HYOBFS_ACL_MAX_NAME) return HYOBFS_ACL_ERR_PATTERN;
+                    if (!d[k].value && d[k].len) return HYOBFS_ERR_INVALID;
+                    rx::Dfa dfa;
+                    if (!rx::compile(d[k].value, d[k].len, dfa)) return HYOBFS_ACL_ERR_REGEX;
+                    if (t.dfa.size() + dfa.cells.size() > 0xFFFFFFFFull) return HYOBFS_ERR_INVALID;
+                    Entry x = e;
+                    x.kind = kRegex;
+                    x.off = (uint32_t)t.dfa.size();
+                    x.tail[0] = dfa.start;
+                    t.dfa.insert(t.dfa.end(), dfa.cells.begin(), dfa.cells.end());
+                    regexes.push_back(x);
+                    continue;
+                }
                 if (d[k].type > HYOBFS_ACL_DOMAIN_FULL) return HYOBFS_ERR_INVALID;
                 const int st = add_pattern(t, e,
                                            d[k].type == HYOBFS_ACL_DOMAIN_FULL ? kExact
@@ -474,6 +503,8 @@ int add_rule(Tables& t, const hyobfs_acl_rule& r, uint32_t index) {
                                            d[k].value, d[k].len);
                 if (st != HYOBFS_OK) return st;
             }
+            t_bad_entry = -1;
+            t.entries.insert(t.entries.end(), regexes.begin(), regexes.end());
             return HYOBFS_OK;
         }
         default: {   // HYOBFS_ACL_CIDR_SET
@@ -509,8 +540,6 @@ int add_rule(Tables& t, const hyobfs_acl_rule& r, uint32_t index) {
     }
 }
 
-thread_local int64_t t_bad_rule = -1;
-
 inline uint64_t up16(uint64_t x) { return (x + 15) / 16 * 16; }
 
 }  // namespace acl
@@ -521,21 +550,27 @@ using namespace hyobfs::acl;
 struct hyobfs_acl_ruleset {
     int device = 0;
     uint32_t n_rules = 0, n_entries = 0;
-    uint8_t* mem = nullptr;   // entries | rule_out | words | pats, each from a 16-byte boundary
+    uint8_t* mem = nullptr;   // entries | rule_out | words | pats | dfa, each from a 16-byte boundary
     const Entry* entries = nullptr;
     const RuleOut* rule_out = nullptr;
     const uint32_t* words = nullptr;
     const uint8_t* pats = nullptr;
+    const uint16_t* dfa = nullptr;
 };
 
 extern "C" {
 
 int hyobfs_acl_ruleset_new(const hyobfs_acl_rule* rules, uint32_t n_rules, int device, hyobfs_acl_ruleset** out) {
-    t_bad_rule = -1;
-    if (!out || (!rules && n_rules)) return HYOBFS_ERR_INVALID;
+    return hyobfs_acl_ruleset_new_flags(rules, n_rules, device, 0, out);
+}
+
+int hyobfs_acl_ruleset_new_flags(const hyobfs_acl_rule* rules, uint32_t n_rules, int device, uint32_t flags,
+                                 hyobfs_acl_ruleset** out) {
+    t_bad_rule = t_bad_entry = -1;
+    if (!out || (!rules && n_rules) || (flags & ~HYOBFS_ACL_FLAG_REGEX)) return HYOBFS_ERR_INVALID;
     Tables t;
     for (uint32_t i = 0; i < n_rules; ++i) {
-        const int st = add_rule(t, rules[i], i);
+        const int st = add_rule(t, rules[i], i, flags);
         if (st != HYOBFS_OK) {
             t_bad_rule = i;
             return st;
@@ -548,12 +583,12 @@ int hyobfs_acl_ruleset_new(const hyobfs_acl_rule* rules, uint32_t n_rules, int d
     auto* s = new (std::nothrow) hyobfs_acl_ruleset();
     if (!s) return HYOBFS_ERR_NOMEM;
     const uint64_t b_ent = up16(t.entries.size() * sizeof(Entry)), b_out = up16(t.rule_out.size() * sizeof(RuleOut)),
-                   b_words = up16(t.words.size() * 4), b_pats = up16(t.pats.size());
+                   b_words = up16(t.words.size() * 4), b_pats = up16(t.pats.size()), b_dfa = up16(t.dfa.size() * 2);
     int prev = -1;
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     hipError_t e = hipSetDevice(device);
     void* mem = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&mem, b_ent + b_out + b_words + b_pats + 16);
+    if (e == hipSuccess) e = hipMalloc(&mem, b_ent + b_out + b_words + b_pats + b_dfa + 16);
     uint8_t* d = static_cast<uint8_t*>(mem);
     if (e == hipSuccess && !t.entries.empty())
         e = hipMemcpy(d, t.entries.data(), t.entries.size() * sizeof(Entry), hipMemcpyHostToDevice);
@@ -563,6 +598,8 @@ int hyobfs_acl_ruleset_new(const hyobfs_acl_rule* rules, uint32_t n_rules, int d
         e = hipMemcpy(d + b_ent + b_out, t.words.data(), t.words.size() * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess && !t.pats.empty())
         e = hipMemcpy(d + b_ent + b_out + b_words, t.pats.data(), t.pats.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !t.dfa.empty())
+        e = hipMemcpy(d + b_ent + b_out + b_words + b_pats, t.dfa.data(), t.dfa.size() * 2, hipMemcpyHostToDevice);
     if (prev >= 0) (void)hipSetDevice(prev);
     if (e != hipSuccess) {
         if (mem) (void)hipFree(mem);
@@ -577,6 +614,7 @@ int hyobfs_acl_ruleset_new(const hyobfs_acl_rule* rules, uint32_t n_rules, int d
     s->rule_out = reinterpret_cast<const RuleOut*>(d + b_ent);
     s->words = reinterpret_cast<const uint32_t*>(d + b_ent + b_out);
     s->pats = d + b_ent + b_out + b_words;
+    s->dfa = reinterpret_cast<const uint16_t*>(d + b_ent + b_out + b_words + b_pats);
     *out = s;
     return HYOBFS_OK;
 }
@@ -591,6 +629,34 @@ uint32_t hyobfs_acl_ruleset_rules(const hyobfs_acl_ruleset* set) { return set ? 
 
 int64_t hyobfs_acl_ruleset_bad_rule(void) { return t_bad_rule; }
 
+int64_t hyobfs_acl_ruleset_bad_entry(void) { return t_bad_entry; }
+
+int hyobfs_acl_regex_check(const uint8_t* pattern, uint32_t len, uint32_t* n_states, uint32_t* n_classes) {
+    if (!pattern && len) return HYOBFS_ERR_INVALID;
+    if (len > HYOBFS_ACL_MAX_NAME) return HYOBFS_ACL_ERR_PATTERN;
+    rx::Dfa dfa;
+    if (!rx::compile(pattern, len, dfa)) return HYOBFS_ACL_ERR_REGEX;
+    if (n_states) *n_states = dfa.states;
+    if (n_classes) *n_classes = dfa.classes;
+    return HYOBFS_OK;
+}
+
+int hyobfs_acl_regex_match(const uint8_t* pattern, uint32_t len, const uint8_t* name, uint32_t name_len) {
+    if ((!pattern && len) || (!name && name_len)) return HYOBFS_ERR_INVALID;
+    if (len > HYOBFS_ACL_MAX_NAME) return HYOBFS_ACL_ERR_PATTERN;
+    // this thread's last pattern stays compiled: one pattern is usually asked about many names
+    thread_local std::vector<uint8_t> last;
+    thread_local rx::Dfa dfa;
+    thread_local bool have = false;
+    if (!have || last.size() != len || !std::equal(last.begin(), last.end(), pattern)) {
+        have = false;
+        if (!rx::compile(pattern, len, dfa)) return HYOBFS_ACL_ERR_REGEX;
+        last.assign(pattern, pattern + len);
+        have = true;
+    }
+    return rx::walk(dfa.cells.data(), dfa.start, name, name_len) ? 1 : 0;
+}
+
 int hyobfs_acl_match_batch(const hyobfs_acl_ruleset* set, const uint8_t* names, const uint64_t* name_off,
                            const uint32_t* name_len, const uint8_t* ipv4, const uint8_t* ipv6, const uint8_t* ip_flags,
                            const uint8_t* proto, const uint16_t* port, uint64_t n, hyobfs_acl_result* res,
@@ -598,7 +664,7 @@ int hyobfs_acl_match_batch(const hyobfs_acl_ruleset* set, const uint8_t* names, 
     if (n == 0) return HYOBFS_OK;
     if (!set || !names || !name_off || !name_len || !proto || !port || !res || (ip_flags && (!ipv4 || !ipv6)))
         return HYOBFS_ERR_INVALID;
-    return launch<kBatch>(Args{set->entries, set->rule_out, set->words, set->pats, set->n_entries, names, name_off,
+    return launch<kBatch>(Args{set->entries, set->rule_out, set->words, set->pats, set->dfa, set->n_entries, names, name_off,
                                name_len, 0, nullptr, ipv4, ipv6, ip_flags, proto, port, n, res},
                           stream);
 }
@@ -609,7 +675,7 @@ int hyobfs_acl_match_sniffed_batch(const hyobfs_acl_ruleset* set, const uint8_t*
                                    hyobfs_acl_result* res, void* stream) {
     if (n == 0) return HYOBFS_OK;
     if (!set || !names || !sres || !proto || !port || !res || (ip_flags && (!ipv4 || !ipv6))) return HYOBFS_ERR_INVALID;
-    return launch<kSniffed>(Args{set->entries, set->rule_out, set->words, set->pats, set->n_entries, names, nullptr,
+    return launch<kSniffed>(Args{set->entries, set->rule_out, set->words, set->pats, set->dfa, set->n_entries, names, nullptr,
                                  nullptr, name_stride, sres, ipv4, ipv6, ip_flags, proto, port, n, res},
                             stream);
 }

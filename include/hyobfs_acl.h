@@ -75,8 +75,16 @@
  *                    "." + value; PLAIN value is a substring of name (the empty
  *                    value always is).  The attribute filter has been applied
  *                    by the caller: only the entries that pass it are handed
- *                    over.  A REGEX entry cannot be matched on the device and
- *                    is refused at creation (HYOBFS_ACL_ERR_REGEX).
+ *                    over.  REGEX: regexp.MatchString(value, name)
+ *                    (matchers_v2geo.go:137-140, :173-182), for a value inside
+ *                    THE REGEX SUBSET below and a rule set made by
+ *                    hyobfs_acl_ruleset_new_flags with HYOBFS_ACL_FLAG_REGEX;
+ *                    every other REGEX entry is refused at creation
+ *                    (HYOBFS_ACL_ERR_REGEX).  The set's result does not depend
+ *                    on the order of its entries, and the device keeps a rule's
+ *                    REGEX entries together after its other entries, so that
+ *                    their walks run side by side in as few 64-entry steps as
+ *                    possible.
  *   CIDR_SET         geoipMatcher.Match (matchers_v2geo.go:48-60): matchIP of
  *                    IPv4 if present, then of IPv6 if present; a hit returns
  *                    !inverse, no hit (also: no address at all) returns
@@ -111,6 +119,54 @@
  * decides nothing for it, whatever the rules are; the caller matches it itself
  * (hysteria_amd/acl.py does).
  *
+ * THE REGEX SUBSET.  The device compiles a REGEX value into a DFA over bytes
+ * (hysteria_amd/csrc/acl_regex.h) and takes it only if every construct in it is
+ * of this list; anything else is refused and never guessed at.  The Go binding
+ * has already run regexp.Compile, so a value that is invalid in Go never arrives:
+ * the device only decides between "mine" and "not mine".
+ *   - literals; '\' followed by a non-alphanumeric ASCII byte, which is that byte
+ *   - \d \D \w \W \s \S, inside classes as well
+ *   - '.'
+ *   - [...] and [^...] with single bytes, ranges and the escapes above
+ *   - ( ) and (?: )
+ *   - '|'; empty branches are allowed ("a|" matches everything, as in Go)
+ *   - * + ? {n} {n,} {n,m} with n, m <= 1000, each optionally followed by one
+ *     lazy '?', which is ignored: laziness does not change whether a match exists
+ *   - '^' and '$' anywhere
+ * Refused with HYOBFS_ACL_ERR_REGEX:
+ *   - any other (?...) form: flags, named groups
+ *   - \b \B \A \z \pX \Q \x.. and every other alphanumeric escape; a
+ *     backslash at the end
+ *   - POSIX [[:...:]] or a '[' inside a class; ']' as the first class member; a
+ *     range that runs backwards or ends in a class escape; an unclosed class
+ *   - a '{' that is not one of the three valid repeat forms (Go reads "a{,3}" as
+ *     literal text, Python as {0,3}), m < n, a count above 1000; a '}' or a ']'
+ *     that closes nothing (write "\}" and "\]")
+ *   - a repeat applied to a repeat, to an anchor or to nothing
+ *   - an unclosed group, a stray ')', groups nested more than 64 deep
+ *   - a pattern byte >= 0x80
+ *   - a DFA of more than HYOBFS_ACL_REGEX_MAX_STATES states ("a.{12}b$" is
+ *     refused for this reason), or counted repeats that expand to more than
+ *     65536 NFA states
+ * A value longer than HYOBFS_ACL_MAX_NAME stays HYOBFS_ACL_ERR_PATTERN.
+ * Semantics (Go regexp, no flags): the match is unanchored on both sides unless
+ * the pattern anchors it; '^' is the beginning of the text and '$' its end (no
+ * multi-line mode); '.' is every byte but '\n'; \s is [\t\n\f\r ]; \w is
+ * [0-9A-Za-z_].  The name is the normalised one of rule 1, as for every other
+ * DOMAIN_SET entry; the pattern is NOT lower-cased, so an upper-case literal
+ * simply never matches.  An empty pattern matches every name; an empty name is
+ * a name.
+ *   TRAP a: Go's \s excludes \v (0x0b); Python's includes it.
+ *   TRAP b: Go's '$' does not match before a trailing '\n'; Python's does
+ *           (Python's \Z is Go's '$').
+ *   TRAP c: at position 0 of an empty name both '^' and '$' hold, so "$^" and
+ *           "^$" match the empty name and nothing else: the start state's
+ *           end-of-text transition is computed with both assertions true.
+ *   TRAP d: '^' after a consumed byte never holds: "a^b" compiles to a DFA that
+ *           never accepts.
+ * The names left to the host (below) are why the device may treat bytes as
+ * runes: every name it matches is ASCII.
+ *
  * STATED DIVERGENCE.  The reference sorts a CIDR set with sort.Slice, which is
  * not stable, so the order of entries with equal addresses is unspecified
  * there.  Here the sort is stable by address bytes with the shorter prefix
@@ -137,7 +193,7 @@ extern "C" {
 /* per-item and creation status, continuing after HYOBFS_SNIFF_ERR_* */
 #define HYOBFS_ACL_ERR_NO_NAME (-61)  /* match_sniffed: sres[i].status != OK or name_len == 0 */
 #define HYOBFS_ACL_ERR_HOST (-62)     /* the name is left to the host (see above) */
-#define HYOBFS_ACL_ERR_REGEX (-63)    /* ruleset_new: a DOMAIN_SET entry of type REGEX */
+#define HYOBFS_ACL_ERR_REGEX (-63)    /* a DOMAIN_SET entry of type REGEX that the device does not take */
 #define HYOBFS_ACL_ERR_PATTERN (-64)  /* ruleset_new: a pattern or set value longer than HYOBFS_ACL_MAX_NAME */
 
 #define HYOBFS_ACL_NO_HIJACK 0xFFFFFFFFu
@@ -201,16 +257,52 @@ typedef struct hyobfs_acl_ruleset hyobfs_acl_ruleset;
  * checked for every rule before the device is looked at: an unknown kind,
  * proto > 2, a bad family or a prefix beyond it, a null pattern with a non-zero
  * length or null entries with a non-zero count (HYOBFS_ERR_INVALID; a domain
- * rule's pattern must not be null at all); a REGEX entry
- * (HYOBFS_ACL_ERR_REGEX); a pattern or value longer than HYOBFS_ACL_MAX_NAME
+ * rule's pattern must not be null at all); a REGEX entry, whatever its value
+ * (HYOBFS_ACL_ERR_REGEX; hyobfs_acl_ruleset_new_flags takes them); a pattern or value longer than HYOBFS_ACL_MAX_NAME
  * (HYOBFS_ACL_ERR_PATTERN).  hyobfs_acl_ruleset_bad_rule() then names the rule.
  * n_rules == 0 is valid (rules may be null): every item gets rule = -1.
  */
 int hyobfs_acl_ruleset_new(const hyobfs_acl_rule* rules, uint32_t n_rules, int device, hyobfs_acl_ruleset** out);
+
+/* hyobfs_acl_ruleset_new_flags: REGEX entries inside the subset are compiled and matched on the device */
+#define HYOBFS_ACL_FLAG_REGEX 1u
+/* the largest DFA a REGEX entry may compile to */
+#define HYOBFS_ACL_REGEX_MAX_STATES 4096
+
+/*
+ * hyobfs_acl_ruleset_new with flags; flags == 0 is that call.  With
+ * HYOBFS_ACL_FLAG_REGEX every REGEX entry is compiled (THE REGEX SUBSET above);
+ * the first one the device cannot take gives HYOBFS_ACL_ERR_REGEX, checked like
+ * every other refusal before the device is looked at:
+ * hyobfs_acl_ruleset_bad_rule() names the rule and hyobfs_acl_ruleset_bad_entry()
+ * the entry within it.  Unknown flag bits: HYOBFS_ERR_INVALID.
+ */
+int hyobfs_acl_ruleset_new_flags(const hyobfs_acl_rule* rules, uint32_t n_rules, int device, uint32_t flags,
+                                 hyobfs_acl_ruleset** out);
 void hyobfs_acl_ruleset_free(hyobfs_acl_ruleset* set);
 uint32_t hyobfs_acl_ruleset_rules(const hyobfs_acl_ruleset* set);
 /* index of the rule that this thread's last failed hyobfs_acl_ruleset_new refused, or -1 */
 int64_t hyobfs_acl_ruleset_bad_rule(void);
+/* index, within that rule's entries as given, of the DOMAIN_SET entry that was refused; -1 when the
+   refusal was not about one entry */
+int64_t hyobfs_acl_ruleset_bad_entry(void);
+
+/*
+ * Host only, no device.  Whether the device takes this REGEX value: HYOBFS_OK
+ * (and, where the pointers are not null, the states of its DFA's subset
+ * construction and its byte classes), HYOBFS_ACL_ERR_REGEX, HYOBFS_ACL_ERR_PATTERN
+ * or HYOBFS_ERR_INVALID (a null pattern with a length).  A binding asks per
+ * entry and keeps on the host only a rule that holds a refused value.
+ */
+int hyobfs_acl_regex_check(const uint8_t* pattern, uint32_t len, uint32_t* n_states, uint32_t* n_classes);
+
+/*
+ * Host only: the scalar counterpart of the kernel's REGEX entry.  Compiles the
+ * value, then runs the walk the kernel runs over name[0, name_len) AS GIVEN
+ * (not normalised; any bytes, any length): 1 match, 0 none, or a negative
+ * status as hyobfs_acl_regex_check gives it.
+ */
+int hyobfs_acl_regex_match(const uint8_t* pattern, uint32_t len, const uint8_t* name, uint32_t name_len);
 
 typedef struct hyobfs_acl_result {
     int32_t status;    /* HYOBFS_OK, HYOBFS_ACL_ERR_NO_NAME or HYOBFS_ACL_ERR_HOST */
