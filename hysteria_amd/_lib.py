@@ -130,6 +130,9 @@ _ACL_SIG = {   # include/hyobfs_acl.h (hysteria_amd/acl.py, which imports the sn
     "hyobfs_acl_ruleset_bad_rule": (_i64, []),
     "hyobfs_acl_ruleset_new_flags": (_i32, [_vp, _u32, _i32, _u32, ctypes.POINTER(_vp)]),
     "hyobfs_acl_ruleset_bad_entry": (_i64, []),
+    "hyobfs_acl_ruleset_new_opts": (_i32, [_vp, _u32, _i32, _vp, ctypes.POINTER(_vp)]),
+    "hyobfs_acl_ruleset_entries": (_u32, [_vp]),
+    "hyobfs_acl_ruleset_index_info": (_i32, [_vp, _u32, _vp]),
     "hyobfs_acl_regex_check": (_i32, [_vp, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "hyobfs_acl_regex_match": (_i32, [_vp, _u32, _vp, _u32]),
     "hyobfs_acl_match_batch": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp]),

@@ -26,7 +26,10 @@ Matching runs in ``libhyobfs.so`` (``include/hyobfs_acl.h`` states the rules and
 the one divergence).  A geosite entry of type regex goes to the device only on
 request (``compile_rules(..., device_regex=True)``) and only if the library takes
 its pattern (``regex_check``; the header's "THE REGEX SUBSET"); without the
-switch such an entry is a CompilationError, as before.  The device leaves three kinds of names to the host (a byte
+switch such an entry is a CompilationError, as before.  The full and root values
+of a large geosite list are looked up in a hash table on the device instead of
+walked one by one, again on request (``compile_rules(..., device_index=True)``;
+the header's "THE INDEX"); no result changes.  The device leaves three kinds of names to the host (a byte
 >= 0x80, ``xn--`` anywhere, more than 255 bytes), because ``domainMatcher`` runs
 ``idna.ToUnicode`` on the name; ``match_many`` finishes exactly those items with
 ``RuleSet.match_host``, which decodes ``xn--`` labels with the standard
@@ -56,6 +59,8 @@ from ._dev import _pack, _ptr, _records, _stream, _to
 MAX_NAME = 255
 NO_HIJACK = 0xFFFFFFFF
 FLAG_REGEX = 1              # HYOBFS_ACL_FLAG_REGEX
+FLAG_INDEX = 2              # HYOBFS_ACL_FLAG_INDEX (hyobfs_acl_options.flags only)
+INDEX_MIN_DEFAULT = 65      # HYOBFS_ACL_INDEX_MIN_DEFAULT
 REGEX_MAX_STATES = 4096     # HYOBFS_ACL_REGEX_MAX_STATES
 PROTO_BOTH, PROTO_TCP, PROTO_UDP = 0, 1, 2
 
@@ -97,6 +102,21 @@ class HyobfsAclRule(ctypes.Structure):
                 ("pad_", ctypes.c_uint8), ("n_entries", ctypes.c_uint32), ("entries", ctypes.c_void_p)]
 
 
+class HyobfsAclOptions(ctypes.Structure):
+    """struct hyobfs_acl_options."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("index_min", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class HyobfsAclIndexInfo(ctypes.Structure):
+    """struct hyobfs_acl_index_info."""
+    _fields_ = [("values", ctypes.c_uint32), ("slots", ctypes.c_uint32), ("max_probe", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+IndexInfo = collections.namedtuple("IndexInfo", "values slots max_probe")
+
+
 def _alib(lib=None):
     """The library with include/hyobfs_acl.h declared (_lib.load() has done it for
     every build that holds these entry points; one without them fails here)."""
@@ -114,13 +134,18 @@ class RuleRefused(ValueError):
         super().__init__(f"{where}: {ERRORS.get(status, 'invalid rule')} ({status})")
 
 
-def ruleset_new(c_rules, n_rules: int, device: int = 0, flags: int = 0):
+def ruleset_new(c_rules, n_rules: int, device: int = 0, flags: int = 0, index_min=None):
     """hyobfs_acl_ruleset_new (``flags`` == 0) or hyobfs_acl_ruleset_new_flags over a
-    HyobfsAclRule array: the handle.  A refused rule raises RuleRefused (before
+    HyobfsAclRule array: the handle.  With ``index_min`` given (0: the library's
+    default), hyobfs_acl_ruleset_new_opts with these flags (FLAG_INDEX is valid
+    there only) and that threshold.  A refused rule raises RuleRefused (before
     the device is looked at)."""
     lib = _alib()
     h = ctypes.c_void_p()
-    if flags:
+    if index_min is not None:
+        opts = HyobfsAclOptions(ctypes.sizeof(HyobfsAclOptions), flags, index_min, 0)
+        st = lib.hyobfs_acl_ruleset_new_opts(c_rules, n_rules, device, ctypes.byref(opts), ctypes.byref(h))
+    elif flags:
         st = lib.hyobfs_acl_ruleset_new_flags(c_rules, n_rules, device, flags, ctypes.byref(h))
     else:
         st = lib.hyobfs_acl_ruleset_new(c_rules, n_rules, device, ctypes.byref(h))
@@ -134,6 +159,19 @@ def ruleset_new(c_rules, n_rules: int, device: int = 0, flags: int = 0):
 
 def ruleset_free(handle) -> None:
     _alib().hyobfs_acl_ruleset_free(handle)
+
+
+def ruleset_entries(handle) -> int:
+    """hyobfs_acl_ruleset_entries: the entries of the table the kernel walks."""
+    return int(_alib().hyobfs_acl_ruleset_entries(handle))
+
+
+def ruleset_index_info(handle, rule: int) -> IndexInfo:
+    """hyobfs_acl_ruleset_index_info: (values, slots, max_probe) of one rule's index;
+    slots == 0 when the rule has none."""
+    info = HyobfsAclIndexInfo()
+    _lib.check(_alib().hyobfs_acl_ruleset_index_info(handle, rule, ctypes.byref(info)), "acl_ruleset_index_info")
+    return IndexInfo(int(info.values), int(info.slots), int(info.max_probe))
 
 
 def _pattern_bytes(p) -> bytes:
@@ -363,7 +401,8 @@ def compile_host_matcher(addr: str, geo=None, device_regex: bool = False) -> Rul
     return Rule(KIND_DOMAIN_EXACT, pattern=addr)
 
 
-def compile_rules(text_rules, outbounds: dict, geo=None, device_regex: bool = False) -> "RuleSet":
+def compile_rules(text_rules, outbounds: dict, geo=None, device_regex: bool = False, device_index: bool = False,
+                  index_min: int = 0) -> "RuleSet":
     """Compile (compile.go:130-161).  ``outbounds`` maps lower-case names to
     integers; ``geo`` (optional) has ``geoip(code)`` returning a list of (address
     bytes, prefix) -- or (that list, inverse) -- and ``geosite(name)`` returning a
@@ -371,7 +410,10 @@ def compile_rules(text_rules, outbounds: dict, geo=None, device_regex: bool = Fa
     "full"; both return None for an unknown name.  A regex entry that passes the
     rule's attribute filter is a CompilationError, unless ``device_regex`` is set:
     then it is kept and matched on the device, and only a pattern that
-    ``regex_check`` refuses is a CompilationError, with the library's status."""
+    ``regex_check`` refuses is a CompilationError, with the library's status.
+    ``device_index``: the device looks the full and root values of a geosite list
+    with at least ``index_min`` of them (0: the library's default, 65) up in a hash
+    table instead of walking them; no result changes."""
     rules = []
     for tr in text_rules:
         if tr.outbound.lower() not in outbounds:
@@ -397,7 +439,7 @@ def compile_rules(text_rules, outbounds: dict, geo=None, device_regex: bool = Fa
         rule.outbound = int(outbounds[tr.outbound.lower()])
         rule.line_num = tr.line_num
         rules.append(rule)
-    return RuleSet(rules)
+    return RuleSet(rules, device_index, index_min)
 
 
 # ------------------------------------------------------------------ the host matcher (names the device leaves)
@@ -551,9 +593,14 @@ def _as_ip(x, size):
 # ------------------------------------------------------------------ the rule set
 class RuleSet:
     """A compiled rule set.  The device copy (hyobfs_acl_ruleset) is made on first
-    use per device and freed by close() / the garbage collector."""
+    use per device and freed by close() / the garbage collector.  ``device_index``:
+    it is made by hyobfs_acl_ruleset_new_opts with HYOBFS_ACL_FLAG_INDEX and
+    ``index_min`` (the header's "THE INDEX"; matching gives the same results)."""
 
-    def __init__(self, rules):
+    def __init__(self, rules, device_index: bool = False, index_min: int = 0):
+        if index_min and not device_index:
+            raise ValueError("index_min needs device_index")
+        self.device_index, self.index_min = bool(device_index), int(index_min)
         self.rules = list(rules)
         self.hijacks = sorted({r.hijack for r in self.rules if r.hijack is not None})
         self._sets = {}
@@ -669,17 +716,20 @@ class RuleSet:
         return arr, keep
 
     def flags(self) -> int:
-        """HYOBFS_ACL_FLAG_REGEX if a rule holds a regex entry, else 0."""
-        return FLAG_REGEX if any(r.kind == KIND_DOMAIN_SET and any(e[0] == "regex" for e in r.entries)
-                                 for r in self.rules) else 0
+        """HYOBFS_ACL_FLAG_REGEX if a rule holds a regex entry, and HYOBFS_ACL_FLAG_INDEX
+        if the set was made with ``device_index``."""
+        regex = any(r.kind == KIND_DOMAIN_SET and any(e[0] == "regex" for e in r.entries) for r in self.rules)
+        return (FLAG_REGEX if regex else 0) | (FLAG_INDEX if self.device_index else 0)
 
     def device_set(self, device: int = 0):
         """The hyobfs_acl_ruleset handle on cuda:<device> (made once); regex entries
-        go over with HYOBFS_ACL_FLAG_REGEX."""
+        go over with HYOBFS_ACL_FLAG_REGEX, and a set made with ``device_index``
+        through hyobfs_acl_ruleset_new_opts."""
         if device not in self._sets:
             arr, keep = self.c_rules()
             try:
-                self._sets[device] = ruleset_new(arr, len(self.rules), device, self.flags())
+                self._sets[device] = ruleset_new(arr, len(self.rules), device, self.flags(),
+                                                 self.index_min if self.device_index else None)
             except RuleRefused as e:
                 line = self.rules[e.rule].line_num if 0 <= e.rule < len(self.rules) else 0
                 raise CompilationError(line, str(e)) from None

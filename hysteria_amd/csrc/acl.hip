@@ -29,7 +29,17 @@
 // bytes in memory.  Addresses are kept as four big-endian words
 // in v4-mapped form, so Equal and Contains with their To4 rules become word
 // compares (hyobfs_acl.h, traps 1 to 3).
+//
+// The index (hyobfs_acl_ruleset_new_opts with HYOBFS_ACL_FLAG_INDEX): the FULL and ROOT
+// values of a large enough DOMAIN_SET are not entries of the walk but one entry of kind
+// kDomainIndex in front of the set's PLAIN and REGEX entries.  Its lane hashes the name
+// in LDS from its end towards its start, and at position 0 and after every '.' looks the
+// suffix that begins there up in the set's open-addressed table of 16-byte slots (hash,
+// offset of the value's bytes, length and type bits): the candidates of hyobfs_acl.h,
+// "THE INDEX".  A hash hit is never a match by itself: the value's bytes are compared.
 #include <algorithm>
+#include <string>
+#include <utility>
 #include <new>
 #include <vector>
 
@@ -50,7 +60,16 @@ constexpr uint32_t kWaves = 4;   // items per workgroup
 constexpr uint32_t kGridCap = HY_ACL_GRID_CAP;
 constexpr uint32_t kNameLds = 256;   // HYOBFS_ACL_MAX_NAME rounded up to whole rounds of 64 lanes
 
-enum : uint32_t { kAll = 0, kIp, kCidr4, kCidr6, kExact, kWildcard, kSuffix, kPlain, kCidrSet, kRegex };
+// Test knob: only the low HY_ACL_INDEX_HASH_BITS bits of an index hash survive, in the stored
+// hash and in the slot choice alike.  The emulated tier builds a second binary with 2, in which
+// every chain is long and wraps round the table's end.
+#ifndef HY_ACL_INDEX_HASH_BITS
+#define HY_ACL_INDEX_HASH_BITS 32
+#endif
+static_assert(HY_ACL_INDEX_HASH_BITS >= 1 && HY_ACL_INDEX_HASH_BITS <= 32, "HY_ACL_INDEX_HASH_BITS");
+constexpr uint32_t kIxHashMask = HY_ACL_INDEX_HASH_BITS >= 32 ? 0xFFFFFFFFu : (1u << (HY_ACL_INDEX_HASH_BITS & 31)) - 1;
+
+enum : uint32_t { kAll = 0, kIp, kCidr4, kCidr6, kExact, kWildcard, kSuffix, kPlain, kCidrSet, kRegex, kDomainIndex };
 enum { kBatch = 0, kSniffed = 1 };
 
 struct alignas(16) Entry {
@@ -68,10 +87,22 @@ struct alignas(16) Entry {
     //                     takes (len less its stars) | that count of literal bytes << 16
     //   kPlain            word 0: the first min(len, 4) bytes of the value, in order
     //   kRegex            word 0: the start state (0, rx::kAccept or rx::kDead)
+    //   kDomainIndex      word 0: the table's slot count - 1 (`off`: its first slot in `slots`)
     uint32_t tail[4];
 };
 static_assert(sizeof(Entry) == 32, "Entry layout");
 constexpr uint32_t kTail = 16, kWildTail = 12, kPlainHead = 4;
+
+// One slot of an indexed set's table: one aligned 16-byte load.  A slot in use holds one distinct
+// value; `meta` 0 is an empty slot and ends a probe sequence.
+struct alignas(16) Slot {
+    uint32_t hash;   // ix_hash of the value: a slot with another hash is passed without a dependent load
+    uint32_t off;    // the value's bytes in `pats`
+    uint32_t meta;   // the value's length | kIxFull and / or kIxRoot | kIxUsed
+    uint32_t pad_;
+};
+static_assert(sizeof(Slot) == 16, "Slot layout");
+constexpr uint32_t kIxLen = 0xFFFF, kIxFull = 1u << 16, kIxRoot = 1u << 17, kIxUsed = 1u << 31;
 
 struct RuleOut {
     uint32_t outbound, hijack;
@@ -83,6 +114,7 @@ struct Args {
     const uint32_t* words;
     const uint8_t* pats;
     const uint16_t* dfa;
+    const Slot* slots;
     uint32_t n_entries;
     const uint8_t* names;
     const uint64_t* name_off;          // kBatch
@@ -200,8 +232,59 @@ HY_HD bool wildcard(const uint8_t* name, uint32_t nl, const uint8_t* p, uint32_t
     return q == pl;
 }
 
+// ---- the index of a DOMAIN_SET's FULL and ROOT values
+// The hash runs from a text's last byte to its first (FNV-1a's step), so one backward pass over
+// a name gives the hash of every suffix; ix_mix spreads it before a slot is taken from its low
+// bits.
+constexpr uint32_t kIxBasis = 2166136261u;
+HY_HD uint32_t ix_step(uint32_t h, uint32_t c) { return (h ^ c) * 16777619u; }
+HY_HD uint32_t ix_mix(uint32_t h) {
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h & kIxHashMask;
+}
+HY_HD uint32_t ix_hash(const uint8_t* v, uint32_t len) {
+    uint32_t h = kIxBasis;
+    for (uint32_t k = len; k-- > 0;) h = ix_step(h, v[k]);
+    return ix_mix(h);
+}
+
+// The candidate name[at, nl) with hash `hash` against one table of mask + 1 slots: linear probing
+// from slot hash & mask DOWNWARDS (so that the weak-hash build, whose sequences all begin in the
+// first slots, goes round the table's end at once) to the first empty slot; the table is at most
+// half full, so there is one.  Values are distinct: the slot whose bytes agree decides, by its
+// type bits (FULL only for the whole name).
+HY_HD bool index_probe(const Slot* slots, uint32_t mask, const uint8_t* pats, const uint8_t* name, uint32_t at,
+                       uint32_t nl, uint32_t hash) {
+    const uint32_t len = nl - at, want = at == 0 ? kIxFull | kIxRoot : kIxRoot;
+    for (uint32_t s = hash & mask;; s = (s - 1) & mask) {
+        const Slot x = slots[s];
+        if (!x.meta) return false;
+        if (x.hash == hash && (x.meta & kIxLen) == len && bytes_eq(name, at, pats + x.off, len)) return (x.meta & want) != 0;
+    }
+}
+
+// Some FULL or ROOT value of the table matches the name (hyobfs_acl.h, "THE INDEX"): the whole
+// name and every suffix that begins right after a '.' are looked up, the shortest first.
+HY_HD bool index_lookup(const Slot* slots, uint32_t mask, const uint8_t* pats, const uint8_t* name, uint32_t nl) {
+    if (nl == 0) return index_probe(slots, mask, pats, name, 0, 0, ix_mix(kIxBasis));
+    uint32_t h = kIxBasis, c = name[nl - 1];
+    for (uint32_t i = nl; i-- > 0;) {
+        const uint32_t before = i ? name[i - 1] : '.';
+        h = ix_step(h, c);
+        if (before == '.' && index_probe(slots, mask, pats, name, i, nl, ix_mix(h))) return true;
+        c = before;
+    }
+    return false;
+}
+
 // One entry against one item: compiledRule.Match (compile.go:62-70).
 // `nt`: the name's last 16 bytes, the last one first, zero past its start.
+// IDX: the rule set has a kDomainIndex entry (a set without one runs the code without that case).
+template <bool IDX>
 HY_HD bool entry_matches(const Entry& e, const Args& a, const uint8_t* name, uint32_t nl, const uint32_t* nt,
                          const Host& h, uint32_t proto, uint32_t port) {
     if (e.proto != 0 && e.proto != proto) return false;
@@ -256,12 +339,14 @@ HY_HD bool entry_matches(const Entry& e, const Args& a, const uint8_t* name, uin
         }
         case kRegex:
             return rx::walk(a.dfa + e.off, e.tail[0], name, nl);
+        case kDomainIndex:
+            return IDX && index_lookup(a.slots + e.off, e.tail[0], a.pats, name, nl);
         default:
             return false;
     }
 }
 
-template <int MODE>
+template <int MODE, bool IDX>
 __global__ __launch_bounds__(64 * kWaves) void acl_kernel(Args a) {
     __shared__ uint8_t name_all[kWaves][kNameLds];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -347,7 +432,7 @@ __global__ __launch_bounds__(64 * kWaves) void acl_kernel(Args a) {
             bool hit = false;
             if (idx < a.n_entries) {
                 e = a.entries[idx];
-                hit = entry_matches(e, a, name, nl, nt, h, proto, port);
+                hit = entry_matches<IDX>(e, a, name, nl, nt, h, proto, port);
             }
             const unsigned long long b = __ballot(hit);
             if (b) {
@@ -369,10 +454,15 @@ inline uint32_t grid_for(uint64_t n) {
     return (uint32_t)(g < kGridCap ? g : kGridCap);
 }
 
+// `indexed`: the rule set has a kDomainIndex entry; every other set runs the kernel without that case
 template <int MODE>
-inline int launch(const Args& a, void* stream) {
-    hipLaunchKernelGGL(acl_kernel<MODE>, dim3(grid_for(a.n)), dim3(64 * kWaves), 0, static_cast<hipStream_t>(stream),
-                       a);
+inline int launch(const Args& a, bool indexed, void* stream) {
+    if (indexed)
+        hipLaunchKernelGGL((acl_kernel<MODE, true>), dim3(grid_for(a.n)), dim3(64 * kWaves), 0,
+                           static_cast<hipStream_t>(stream), a);
+    else
+        hipLaunchKernelGGL((acl_kernel<MODE, false>), dim3(grid_for(a.n)), dim3(64 * kWaves), 0,
+                           static_cast<hipStream_t>(stream), a);
     return hy_status(hipGetLastError());
 }
 
@@ -387,6 +477,8 @@ struct Tables {
     std::vector<uint32_t> words;
     std::vector<uint8_t> pats;
     std::vector<uint16_t> dfa;
+    std::vector<Slot> slots;
+    std::vector<hyobfs_acl_index_info> index;   // per rule; slots == 0: the rule has no index
 };
 
 thread_local int64_t t_bad_rule = -1, t_bad_entry = -1;
@@ -431,10 +523,50 @@ inline int add_pattern(Tables& t, Entry e, uint32_t kind, const uint8_t* p, uint
     return HYOBFS_OK;
 }
 
-// One compiledRule into the tables; a status other than OK refuses the rule.
-int add_rule(Tables& t, const hyobfs_acl_rule& r, uint32_t index, uint32_t flags) {
+// The table of an indexed set: `vals` are its FULL and ROOT values, each with its type bit, and
+// `entry` is the set's kDomainIndex entry.  Duplicate values are merged (a value given as both
+// types keeps both bits); the slot count is the power of two that leaves the table at most half
+// full; the values go in in sorted order, so the table does not depend on the order given.
+inline int add_index(Tables& t, size_t entry, std::vector<std::pair<std::string, uint32_t>>& vals,
+                     hyobfs_acl_index_info& info) {
+    std::sort(vals.begin(), vals.end());
+    size_t n = 0;
+    for (size_t k = 0; k < vals.size(); ++k) {
+        if (n && vals[n - 1].first == vals[k].first) {
+            vals[n - 1].second |= vals[k].second;
+        } else {
+            if (n != k) vals[n] = std::move(vals[k]);
+            ++n;
+        }
+    }
+    vals.resize(n);
+    uint64_t slots = 2;
+    while (slots < 2 * (uint64_t)n) slots <<= 1;
+    if (t.slots.size() + slots > 0xFFFFFFFFull) return HYOBFS_ERR_INVALID;
+    const uint32_t first = (uint32_t)t.slots.size(), mask = (uint32_t)slots - 1;
+    t.slots.resize(first + slots);   // all empty
+    uint32_t longest = 0;
+    for (const auto& v : vals) {
+        const auto* p = reinterpret_cast<const uint8_t*>(v.first.data());
+        const uint32_t len = (uint32_t)v.first.size(), hash = ix_hash(p, len);
+        uint32_t s = hash & mask, probes = 1;
+        for (; t.slots[first + s].meta; ++probes) s = (s - 1) & mask;
+        t.slots[first + s] = Slot{hash, (uint32_t)t.pats.size(), len | v.second | kIxUsed, 0};
+        t.pats.insert(t.pats.end(), p, p + len);
+        longest = std::max(longest, probes);
+    }
+    t.entries[entry].off = first;
+    t.entries[entry].tail[0] = mask;
+    info = hyobfs_acl_index_info{(uint32_t)n, (uint32_t)slots, longest, 0};
+    return HYOBFS_OK;
+}
+
+// One compiledRule into the tables; a status other than OK refuses the rule.  `index_min`: a
+// DOMAIN_SET with at least this many FULL + ROOT entries is indexed; 0: none is.
+int add_rule(Tables& t, const hyobfs_acl_rule& r, uint32_t index, uint32_t flags, uint32_t index_min) {
     if (r.kind > HYOBFS_ACL_CIDR_SET || r.proto > 2) return HYOBFS_ERR_INVALID;
     t.rule_out.push_back(RuleOut{r.outbound, r.hijack});
+    t.index.push_back(hyobfs_acl_index_info{0, 0, 0, 0});
     Entry e{};
     e.rule = index;
     e.proto = (uint8_t)r.proto;
@@ -477,10 +609,34 @@ int add_rule(Tables& t, const hyobfs_acl_rule& r, uint32_t index, uint32_t flags
         case HYOBFS_ACL_DOMAIN_SET: {
             if (!r.entries && r.n_entries) return HYOBFS_ERR_INVALID;
             const auto* d = static_cast<const hyobfs_acl_domain*>(r.entries);
+            // indexed: its FULL and ROOT values are one kDomainIndex entry at the rule's position
+            // and leave the walk; the count is of the entries as given, duplicates included
+            bool indexed = false;
+            if (index_min) {
+                uint64_t fr = 0;
+                for (uint32_t k = 0; k < r.n_entries; ++k)
+                    fr += d[k].type == HYOBFS_ACL_DOMAIN_ROOT || d[k].type == HYOBFS_ACL_DOMAIN_FULL;
+                indexed = fr >= index_min;
+            }
+            const size_t at = t.entries.size();
+            std::vector<std::pair<std::string, uint32_t>> vals;
+            if (indexed) {
+                Entry x = e;
+                x.kind = kDomainIndex;
+                t.entries.push_back(x);
+            }
             // the regex entries after the others (the set's result does not depend on the order)
             std::vector<Entry> regexes;
             for (uint32_t k = 0; k < r.n_entries; ++k) {
                 t_bad_entry = k;
+                if (indexed && (d[k].type == HYOBFS_ACL_DOMAIN_ROOT || d[k].type == HYOBFS_ACL_DOMAIN_FULL)) {
+                    if (d[k].len > HYOBFS_ACL_MAX_NAME) return HYOBFS_ACL_ERR_PATTERN;
+                    if (!d[k].value && d[k].len) return HYOBFS_ERR_INVALID;
+                    vals.emplace_back(d[k].len ? std::string(reinterpret_cast<const char*>(d[k].value), d[k].len)
+                                               : std::string(),
+                                      d[k].type == HYOBFS_ACL_DOMAIN_FULL ? kIxFull : kIxRoot);
+                    continue;
+                }
                 if (d[k].type == HYOBFS_ACL_DOMAIN_REGEX) {
                     if (!(flags & HYOBFS_ACL_FLAG_REGEX)) return HYOBFS_ACL_ERR_REGEX;
                     if (d[k].len > HYOBFS_ACL_MAX_NAME) return HYOBFS_ACL_ERR_PATTERN;
@@ -505,7 +661,7 @@ int add_rule(Tables& t, const hyobfs_acl_rule& r, uint32_t index, uint32_t flags
             }
             t_bad_entry = -1;
             t.entries.insert(t.entries.end(), regexes.begin(), regexes.end());
-            return HYOBFS_OK;
+            return indexed ? add_index(t, at, vals, t.index[index]) : HYOBFS_OK;
         }
         default: {   // HYOBFS_ACL_CIDR_SET
             if (!r.entries && r.n_entries) return HYOBFS_ERR_INVALID;
@@ -550,27 +706,23 @@ using namespace hyobfs::acl;
 struct hyobfs_acl_ruleset {
     int device = 0;
     uint32_t n_rules = 0, n_entries = 0;
-    uint8_t* mem = nullptr;   // entries | rule_out | words | pats | dfa, each from a 16-byte boundary
+    uint8_t* mem = nullptr;   // entries | rule_out | words | pats | dfa | slots, each from a 16-byte boundary
     const Entry* entries = nullptr;
     const RuleOut* rule_out = nullptr;
     const uint32_t* words = nullptr;
     const uint8_t* pats = nullptr;
     const uint16_t* dfa = nullptr;
+    const Slot* slots = nullptr;
+    bool indexed = false;                       // some rule has an index: the kernel with that case runs
+    std::vector<hyobfs_acl_index_info> index;   // per rule
 };
 
-extern "C" {
-
-int hyobfs_acl_ruleset_new(const hyobfs_acl_rule* rules, uint32_t n_rules, int device, hyobfs_acl_ruleset** out) {
-    return hyobfs_acl_ruleset_new_flags(rules, n_rules, device, 0, out);
-}
-
-int hyobfs_acl_ruleset_new_flags(const hyobfs_acl_rule* rules, uint32_t n_rules, int device, uint32_t flags,
-                                 hyobfs_acl_ruleset** out) {
-    t_bad_rule = t_bad_entry = -1;
-    if (!out || (!rules && n_rules) || (flags & ~HYOBFS_ACL_FLAG_REGEX)) return HYOBFS_ERR_INVALID;
+// The three creation calls.  `index_min` 0: no set is indexed.
+static int ruleset_make(const hyobfs_acl_rule* rules, uint32_t n_rules, int device, uint32_t flags, uint32_t index_min,
+                        hyobfs_acl_ruleset** out) {
     Tables t;
     for (uint32_t i = 0; i < n_rules; ++i) {
-        const int st = add_rule(t, rules[i], i, flags);
+        const int st = add_rule(t, rules[i], i, flags, index_min);
         if (st != HYOBFS_OK) {
             t_bad_rule = i;
             return st;
@@ -583,12 +735,13 @@ int hyobfs_acl_ruleset_new_flags(const hyobfs_acl_rule* rules, uint32_t n_rules,
     auto* s = new (std::nothrow) hyobfs_acl_ruleset();
     if (!s) return HYOBFS_ERR_NOMEM;
     const uint64_t b_ent = up16(t.entries.size() * sizeof(Entry)), b_out = up16(t.rule_out.size() * sizeof(RuleOut)),
-                   b_words = up16(t.words.size() * 4), b_pats = up16(t.pats.size()), b_dfa = up16(t.dfa.size() * 2);
+                   b_words = up16(t.words.size() * 4), b_pats = up16(t.pats.size()), b_dfa = up16(t.dfa.size() * 2),
+                   b_slots = t.slots.size() * sizeof(Slot);
     int prev = -1;
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     hipError_t e = hipSetDevice(device);
     void* mem = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&mem, b_ent + b_out + b_words + b_pats + b_dfa + 16);
+    if (e == hipSuccess) e = hipMalloc(&mem, b_ent + b_out + b_words + b_pats + b_dfa + b_slots + 16);
     uint8_t* d = static_cast<uint8_t*>(mem);
     if (e == hipSuccess && !t.entries.empty())
         e = hipMemcpy(d, t.entries.data(), t.entries.size() * sizeof(Entry), hipMemcpyHostToDevice);
@@ -600,6 +753,8 @@ int hyobfs_acl_ruleset_new_flags(const hyobfs_acl_rule* rules, uint32_t n_rules,
         e = hipMemcpy(d + b_ent + b_out + b_words, t.pats.data(), t.pats.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess && !t.dfa.empty())
         e = hipMemcpy(d + b_ent + b_out + b_words + b_pats, t.dfa.data(), t.dfa.size() * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !t.slots.empty())
+        e = hipMemcpy(d + b_ent + b_out + b_words + b_pats + b_dfa, t.slots.data(), b_slots, hipMemcpyHostToDevice);
     if (prev >= 0) (void)hipSetDevice(prev);
     if (e != hipSuccess) {
         if (mem) (void)hipFree(mem);
@@ -615,8 +770,38 @@ int hyobfs_acl_ruleset_new_flags(const hyobfs_acl_rule* rules, uint32_t n_rules,
     s->words = reinterpret_cast<const uint32_t*>(d + b_ent + b_out);
     s->pats = d + b_ent + b_out + b_words;
     s->dfa = reinterpret_cast<const uint16_t*>(d + b_ent + b_out + b_words + b_pats);
+    s->slots = reinterpret_cast<const Slot*>(d + b_ent + b_out + b_words + b_pats + b_dfa);
+    s->indexed = !t.slots.empty();
+    s->index = std::move(t.index);
     *out = s;
     return HYOBFS_OK;
+}
+
+extern "C" {
+
+int hyobfs_acl_ruleset_new(const hyobfs_acl_rule* rules, uint32_t n_rules, int device, hyobfs_acl_ruleset** out) {
+    return hyobfs_acl_ruleset_new_flags(rules, n_rules, device, 0, out);
+}
+
+int hyobfs_acl_ruleset_new_flags(const hyobfs_acl_rule* rules, uint32_t n_rules, int device, uint32_t flags,
+                                 hyobfs_acl_ruleset** out) {
+    t_bad_rule = t_bad_entry = -1;
+    if (!out || (!rules && n_rules) || (flags & ~HYOBFS_ACL_FLAG_REGEX)) return HYOBFS_ERR_INVALID;
+    return ruleset_make(rules, n_rules, device, flags, 0, out);
+}
+
+int hyobfs_acl_ruleset_new_opts(const hyobfs_acl_rule* rules, uint32_t n_rules, int device,
+                                const hyobfs_acl_options* opts, hyobfs_acl_ruleset** out) {
+    if (!opts) return hyobfs_acl_ruleset_new(rules, n_rules, device, out);
+    t_bad_rule = t_bad_entry = -1;
+    if (!out || (!rules && n_rules)) return HYOBFS_ERR_INVALID;
+    if (opts->struct_size != sizeof(hyobfs_acl_options) || opts->reserved != 0 ||
+        (opts->flags & ~(HYOBFS_ACL_FLAG_REGEX | HYOBFS_ACL_FLAG_INDEX)))
+        return HYOBFS_ERR_INVALID;
+    const bool index = (opts->flags & HYOBFS_ACL_FLAG_INDEX) != 0;
+    if (!index && opts->index_min != 0) return HYOBFS_ERR_INVALID;
+    return ruleset_make(rules, n_rules, device, opts->flags & HYOBFS_ACL_FLAG_REGEX,
+                        !index ? 0 : opts->index_min ? opts->index_min : HYOBFS_ACL_INDEX_MIN_DEFAULT, out);
 }
 
 void hyobfs_acl_ruleset_free(hyobfs_acl_ruleset* set) {
@@ -626,6 +811,14 @@ void hyobfs_acl_ruleset_free(hyobfs_acl_ruleset* set) {
 }
 
 uint32_t hyobfs_acl_ruleset_rules(const hyobfs_acl_ruleset* set) { return set ? set->n_rules : 0; }
+
+uint32_t hyobfs_acl_ruleset_entries(const hyobfs_acl_ruleset* set) { return set ? set->n_entries : 0; }
+
+int hyobfs_acl_ruleset_index_info(const hyobfs_acl_ruleset* set, uint32_t rule, hyobfs_acl_index_info* out) {
+    if (!set || !out || rule >= set->n_rules) return HYOBFS_ERR_INVALID;
+    *out = set->index[rule];
+    return HYOBFS_OK;
+}
 
 int64_t hyobfs_acl_ruleset_bad_rule(void) { return t_bad_rule; }
 
@@ -664,9 +857,9 @@ int hyobfs_acl_match_batch(const hyobfs_acl_ruleset* set, const uint8_t* names, 
     if (n == 0) return HYOBFS_OK;
     if (!set || !names || !name_off || !name_len || !proto || !port || !res || (ip_flags && (!ipv4 || !ipv6)))
         return HYOBFS_ERR_INVALID;
-    return launch<kBatch>(Args{set->entries, set->rule_out, set->words, set->pats, set->dfa, set->n_entries, names, name_off,
-                               name_len, 0, nullptr, ipv4, ipv6, ip_flags, proto, port, n, res},
-                          stream);
+    return launch<kBatch>(Args{set->entries, set->rule_out, set->words, set->pats, set->dfa, set->slots, set->n_entries,
+                               names, name_off, name_len, 0, nullptr, ipv4, ipv6, ip_flags, proto, port, n, res},
+                          set->indexed, stream);
 }
 
 int hyobfs_acl_match_sniffed_batch(const hyobfs_acl_ruleset* set, const uint8_t* names, uint32_t name_stride,
@@ -675,9 +868,9 @@ int hyobfs_acl_match_sniffed_batch(const hyobfs_acl_ruleset* set, const uint8_t*
                                    hyobfs_acl_result* res, void* stream) {
     if (n == 0) return HYOBFS_OK;
     if (!set || !names || !sres || !proto || !port || !res || (ip_flags && (!ipv4 || !ipv6))) return HYOBFS_ERR_INVALID;
-    return launch<kSniffed>(Args{set->entries, set->rule_out, set->words, set->pats, set->dfa, set->n_entries, names, nullptr,
-                                 nullptr, name_stride, sres, ipv4, ipv6, ip_flags, proto, port, n, res},
-                            stream);
+    return launch<kSniffed>(Args{set->entries, set->rule_out, set->words, set->pats, set->dfa, set->slots, set->n_entries,
+                                 names, nullptr, nullptr, name_stride, sres, ipv4, ipv6, ip_flags, proto, port, n, res},
+                            set->indexed, stream);
 }
 
 }  // extern "C"

@@ -167,6 +167,32 @@
  * The names left to the host (below) are why the device may treat bytes as
  * runes: every name it matches is ASCII.
  *
+ * THE INDEX.  A DOMAIN_SET of geosite size (cn: 65,029 entries) is too long to
+ * walk entry by entry.  hyobfs_acl_ruleset_new_opts with HYOBFS_ACL_FLAG_INDEX
+ * puts the FULL and ROOT values of a large enough set into a hash table on the
+ * device and looks the name up instead.  The match rule, restated from
+ * matchers_v2geo.go:141-147 for the normalised name of rule 1 (length nl):
+ *   FULL v  matches iff name == v.
+ *   ROOT v  matches iff name == v, or there is an i >= 1 with name[i-1] == '.'
+ *           and name[i:] == v.
+ * So the candidates of a name are its whole text (for FULL and ROOT values) and
+ * every suffix that begins right after a '.' (for ROOT values only): at most 128
+ * for a name of 255 bytes.  Each candidate is looked up; a hash hit is never a
+ * match by itself, the value's bytes are compared, all of them.  The rule has no
+ * exceptions: ROOT ".b" matches "a..b"; ROOT "value" matches ".value"; ROOT ""
+ * and FULL "" match the empty name and nothing else (a normalised name does not
+ * end in '.'); a value with an upper-case letter, a byte >= 0x80, "xn--" or a
+ * trailing dot matches no name the device decides.  A set's result does not
+ * depend on the order of its entries, so "some indexed value matches" is the
+ * predicate of the linear walk over the same values: THE INDEX CHANGES NO
+ * RESULT, only the time a large set takes.  Duplicate values are merged; a value
+ * given as FULL and as ROOT is one value of both types.  PLAIN and REGEX entries
+ * of an indexed set stay entries of the walk, after the set's index; the rule's
+ * proto and ports gate the index as they gate every entry.  The rules
+ * DOMAIN_EXACT / _SUFFIX / _WILDCARD are never indexed.
+ * What counts toward index_min: the set's entries of type FULL or ROOT as given
+ * (duplicates included; PLAIN and REGEX entries do not count).
+ *
  * STATED DIVERGENCE.  The reference sorts a CIDR set with sort.Slice, which is
  * not stable, so the order of entries with equal addresses is unspecified
  * there.  Here the sort is stable by address bytes with the shorter prefix
@@ -279,8 +305,49 @@ int hyobfs_acl_ruleset_new(const hyobfs_acl_rule* rules, uint32_t n_rules, int d
  */
 int hyobfs_acl_ruleset_new_flags(const hyobfs_acl_rule* rules, uint32_t n_rules, int device, uint32_t flags,
                                  hyobfs_acl_ruleset** out);
+
+/* hyobfs_acl_options.flags only (hyobfs_acl_ruleset_new_flags refuses it): THE INDEX above */
+#define HYOBFS_ACL_FLAG_INDEX 2u
+/* more FULL + ROOT values than one 64-entry step of the walk holds */
+#define HYOBFS_ACL_INDEX_MIN_DEFAULT 65u
+
+typedef struct hyobfs_acl_options {
+    uint32_t struct_size; /* sizeof(hyobfs_acl_options); anything else: HYOBFS_ERR_INVALID */
+    uint32_t flags;       /* HYOBFS_ACL_FLAG_REGEX | HYOBFS_ACL_FLAG_INDEX; other bits: HYOBFS_ERR_INVALID */
+    uint32_t index_min;   /* with FLAG_INDEX: a DOMAIN_SET with at least this many FULL + ROOT entries is
+                             indexed; 0 = HYOBFS_ACL_INDEX_MIN_DEFAULT; 1 = every set that has one.
+                             Without FLAG_INDEX it must be 0 */
+    uint32_t reserved;    /* 0 */
+} hyobfs_acl_options;     /* 16 bytes */
+
+/*
+ * hyobfs_acl_ruleset_new with options; opts == NULL is that call.  The options
+ * are checked first (HYOBFS_ERR_INVALID, bad_rule() == -1), then the rules as by
+ * hyobfs_acl_ruleset_new_flags with the REGEX bit of opts->flags, all before the
+ * device is looked at; hyobfs_acl_ruleset_bad_rule() and _bad_entry() name rule
+ * and entry as there (an indexed value longer than HYOBFS_ACL_MAX_NAME is
+ * HYOBFS_ACL_ERR_PATTERN like any other).  With HYOBFS_ACL_FLAG_INDEX every
+ * DOMAIN_SET that reaches index_min gets an index (THE INDEX above, which also
+ * says what counts); every other set, and every set without the flag, is
+ * compiled exactly as by the other two calls.  The index changes no result.
+ */
+int hyobfs_acl_ruleset_new_opts(const hyobfs_acl_rule* rules, uint32_t n_rules, int device,
+                                const hyobfs_acl_options* opts, hyobfs_acl_ruleset** out);
 void hyobfs_acl_ruleset_free(hyobfs_acl_ruleset* set);
 uint32_t hyobfs_acl_ruleset_rules(const hyobfs_acl_ruleset* set);
+/* entries of the table the kernel walks, 64 per step: an indexed set counts one for its index and
+   one for each of its PLAIN and REGEX entries; 0 for a null set */
+uint32_t hyobfs_acl_ruleset_entries(const hyobfs_acl_ruleset* set);
+
+typedef struct hyobfs_acl_index_info {
+    uint32_t values;    /* distinct FULL / ROOT values in the table */
+    uint32_t slots;     /* power of two, at least 2 * values; 0 = this rule has no index */
+    uint32_t max_probe; /* longest probe sequence of any stored value, in slots looked at (1: none collided) */
+    uint32_t reserved;
+} hyobfs_acl_index_info;
+/* the index of rule `rule`, all zero if it has none; a null pointer or rule >= the rule count:
+   HYOBFS_ERR_INVALID */
+int hyobfs_acl_ruleset_index_info(const hyobfs_acl_ruleset* set, uint32_t rule, hyobfs_acl_index_info* out);
 /* index of the rule that this thread's last failed hyobfs_acl_ruleset_new refused, or -1 */
 int64_t hyobfs_acl_ruleset_bad_rule(void);
 /* index, within that rule's entries as given, of the DOMAIN_SET entry that was refused; -1 when the
